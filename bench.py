@@ -1,7 +1,7 @@
 """
 Benchmark of the hot path: full solves of a batch of independent train-control OCPs on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the HIP solver over one batch of synthetic scenarios that is already resident in HBM.
 Workload = BASELINE.json configs[1]: B = 1024 scenarios per GPU, N = 100 shooting
@@ -20,10 +20,19 @@ no torch.distributed): the other dispatch style of SURVEY 8e, same sharding.
 Prints ONE JSON line on rank 0.  `roofline` prices the solve kernel with the streaming model S of SURVEY.md section 8d
 (904 B per stage-iteration) as the contract prescribes, and says next to it what the counters say: the compulsory bytes, the bytes
 the TCC counters saw (profiles/hbm_traffic.json, per workload, digest-checked against the running library) and what really bounds
-the kernel (`limiter`: the double-precision issue rate and exposed latency of one wave per SIMD).  `cpu_baseline` times the CPU
-oracle (a port, not the reference's CasADi/IPOPT, which cannot run here) on the host cores and on one thread; `alt` (N = 1 only)
-carries the other workloads of SURVEY 8(d): the reference's starting point on config 1, configs 2-4 at their per-GPU sizes, the
-other transcriptions.  `--workload c4` measures the shrinking-horizon loop itself (a step = 50 re-solves of every scenario).
+the kernel (`limiter`: the double-precision issue rate and exposed latency of one wave per SIMD).  `--workload c4` measures the
+shrinking-horizon loop itself (a step = 50 re-solves of every scenario).
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, the line.  `--full` adds the legs
+that take runs of their own (one GPU only): `cpu_baseline` times the CPU oracle (a port, not the reference's CasADi/IPOPT, which cannot
+run here) on the host cores and on one thread; `alt` carries the other workloads of SURVEY 8(d): the reference's starting point on
+config 1, configs 2-4 at their per-GPU sizes, the other transcriptions.
+
+`--dump-outputs DIR` writes what the last timed step computed -- the arrays a caller of the timed path receives -- as DIR/<name>.npy
+(float64) after the timed region: `z` (B, nz: the primal solution of every scenario), `cost`, `status`, `iterations` (B,); for
+`--workload c4` the log of the last loop, `cost`, `status`, `iterations`, `t0`, `v0`, `T` (re-solves, B).  The scenarios are seeded, so
+two runs with the same arguments solve the same batch.  Ranks beyond a single process write `<name>_rank<r>.npy`, a process that drives
+several devices stacks them along the first axis.
 """
 
 import argparse
@@ -81,8 +90,12 @@ def parse_args(argv=None):
     ap.add_argument('--warmup', type=int, default=None, help='untimed warm-up steps (default 10; c4: 1)')
     ap.add_argument('--batch', type=int, default=0, help='scenarios per GPU (default: the workload\'s per-GPU size)')
     ap.add_argument('--intervals', type=int, default=0, help='shooting intervals (default: the workload\'s)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-alt', action='store_true', help='skip the extra workloads (reference start, configs 2-4)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs that take runs of their own (one GPU only): the CPU baseline and the extra workloads (`cpu_baseline`, `alt`)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-alt', action='store_true', help='with --full: skip the extra workloads (reference start, configs 2-4)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float64), after the timed region')
     ap.add_argument('--no-build', action='store_true', help='never compile (profiled runs): exit non-zero when the library is stale')
     ap.add_argument('--start', default='profile', choices=['profile', 'reference'],
                     help="starting point of every solve: 'profile' (library default, built on the device from the scenario) or 'reference' (cold start of ocp.py:325-339)")
@@ -128,8 +141,8 @@ def launch_ranks(args):
 PER_GPU_BATCH = dict(c1=1024, c2=8192, c3=8192, c4=512)
 
 
-def measure(solver, scen, overrides, steps, warmup, barrier=None):
-    "Timed region: `steps` launches over a batch resident in HBM.  Returns (elapsed s, kernel ms per launch, stats array)."
+def measure(solver, scen, overrides, steps, warmup, barrier=None, keep_z=False):
+    "Timed region: `steps` launches over a batch resident in HBM.  Returns (elapsed s, kernel ms per launch, stats array); keep_z: the solutions of the last launch in measure.z."
 
     import numpy as np
     from mseetc._device import ST, OV
@@ -168,6 +181,10 @@ def measure(solver, scen, overrides, steps, warmup, barrier=None):
 
     st = np.zeros((B, ST['COUNT']))
     prob.to_host(st, d_st)
+    measure.z = None
+    if keep_z:
+        measure.z = np.zeros((B, prob.nz))
+        prob.to_host(measure.z, d_z)
     measure.first_pass_ms = prob.first_pass_ms()[0]                                     # (side channel: the callers that want it read it right after the call)
     measure.listed_per_launch = (prob.follow_counts()[0] - listed0)/max(steps, 1)      # scenarios the first pass handed to the follow-up kernel
     prob.time_first_pass(False)
@@ -177,6 +194,7 @@ def measure(solver, scen, overrides, steps, warmup, barrier=None):
     return elapsed, kernel_ms_total/steps, st
 
 
+measure.z = None
 measure.first_pass_ms = None
 measure.listed_per_launch = None
 
@@ -213,7 +231,7 @@ def build_workload(name, B, N, rank, start, device, transcription='rk'):
     return solver, solver._scenarios(T, 0, 1, 1), overrides, text
 
 
-def measure_single_process(solver, scen, overrides, steps, warmup, ndev):
+def measure_single_process(solver, scen, overrides, steps, warmup, ndev, keep_z=False):
     """
     The other dispatch style of SURVEY 8e: this process drives `ndev` devices, one handle and one stream each, the batch of
     every device resident in its HBM.  Returns (elapsed s, worst kernel ms per launch, stats of all devices stacked).
@@ -252,8 +270,11 @@ def measure_single_process(solver, scen, overrides, steps, warmup, ndev):
         prob.synchronize()
     elapsed = time.perf_counter() - t0
     st = np.zeros((len(probs), B, ST['COUNT']))
+    measure.z = np.zeros((len(probs)*B, probs[0].nz)) if keep_z else None
     for k, (prob, b) in enumerate(zip(probs, bufs)):
         prob.to_host(st[k], b[2])
+        if keep_z:
+            prob.to_host(measure.z[k*B:(k + 1)*B], b[1])
         for d in b:
             if d is not None:
                 prob.free(d)
@@ -297,12 +318,26 @@ def measure_mpc(train, track, N, T, steps, warmup, device, warm=True, barrier=No
     elapsed = time.perf_counter() - t0
     if loop is not None:
         loop.close()
+    measure_mpc.last_log = log
     stage_iters = float(sum(l['numIntervals']*l['iterations'].sum() for l in log))
     info = {"resolves_per_loop": len(log), "scenarios": len(T), "successful": good, "failed": failed, "arrival_time_relaxed": relaxed,
             "ip_iterations_mean": float(np.mean([l['iterations'].mean() for l in log])),
             "kernel_ms_per_loop": float(sum(l['kernel_ms'] for l in log)), "stage_iterations_per_loop": stage_iters,
             "loop": "host" if host_loop else "device"}
     return elapsed, info
+
+
+measure_mpc.last_log = None
+
+
+def dump_outputs(directory, arrays, rank, world):
+    "The outputs of the last timed step as <directory>/<name>.npy (float64); `_rank<r>` in the name when several ranks write."
+
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ('' if world == 1 else '_rank%d' % rank) + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def summarize(B, N, steps, elapsed, launch_ms, st):
@@ -503,6 +538,9 @@ def main():
         else:
             good_all, failed_all = info['successful'], info['failed']
         gf = group_fields()
+        if args.dump_outputs:
+            log = measure_mpc.last_log
+            dump_outputs(args.dump_outputs, {k: np.stack([np.asarray(l[k], dtype=np.float64) for l in log]) for k in ('cost', 'status', 'iterations', 't0', 'v0', 'T')}, rank, world)
         if rank == 0:
             from mseetc.ocp import casadiSolver
             probe = casadiSolver(train, track, wl.options(N), device=local_rank)
@@ -535,15 +573,19 @@ def main():
 
     first_ms, listed = None, None
     if args.single_process:
-        elapsed, launch_ms, st = measure_single_process(solver, scen, overrides, args.steps, args.warmup, ndrive)
+        elapsed, launch_ms, st = measure_single_process(solver, scen, overrides, args.steps, args.warmup, ndrive, keep_z=bool(args.dump_outputs))
     else:
-        elapsed, launch_ms, st = measure(solver, scen, overrides, args.steps, args.warmup, barrier)
+        elapsed, launch_ms, st = measure(solver, scen, overrides, args.steps, args.warmup, barrier, keep_z=bool(args.dump_outputs))
         first_ms, listed = (measure.first_pass_ms or None), measure.listed_per_launch
 
     if grouped:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        scale = 1.0 if solver.energyOptimal else solver.scalingFactorObjective      # (as solveBatch reports the cost)
+        dump_outputs(args.dump_outputs, {"z": measure.z, "cost": st[:, ST['OBJ']]*scale, "status": st[:, ST['STATUS']], "iterations": st[:, ST['ITERS']]}, rank, world)
 
     n_ok = int(np.sum(st[:, ST['STATUS']] >= 0))
     iters = st[:, ST['ITERS']]
@@ -595,10 +637,10 @@ def main():
 
         solver.close()
 
-        if world == 1 and not args.single_process and not args.no_alt and args.workload == 'c1' and args.transcription == 'rk':
+        if args.full and world == 1 and not args.single_process and not args.no_alt and args.workload == 'c1' and args.transcription == 'rk':
             line["alt"] = alt_workloads(args, local_rank)
 
-        if not args.no_cpu_baseline and world == 1 and not args.single_process and args.transcription == 'rk':
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.single_process and args.transcription == 'rk':
             line["cpu_baseline"] = cpu_baseline(solver, scen, args.start, overrides is not None)
 
         print(json.dumps(line), flush=True)

@@ -26,22 +26,29 @@ ST = dict(STATUS=0, ITERS=1, OBJ=2, KKT=3, MU=4, DUAL_INF=5, CONSTR_VIOL=6, COMP
 _lib = None
 
 
+def _digest():
+    "Content hash of the sources (not file times: a copy of the tree does not keep those in any useful order)."
+
+    import hashlib
+    src = [HERE / 'ms_oracle.c', HERE / 'ms_oracle.h']
+    return hashlib.sha256(b''.join(s.read_bytes() for s in src + [HERE / 'Makefile'] if s.exists())).hexdigest()
+
+
+def stale():
+    "True when oracle/libms_oracle.so is missing or was built from other sources than the ones in the tree."
+
+    so, stamp = HERE / 'libms_oracle.so', HERE / 'libms_oracle.so.stamp'
+    return not so.exists() or not stamp.exists() or stamp.read_text().strip() != _digest()
+
+
 def build(force=False):
     "Compile oracle/libms_oracle.so with gcc (no-op when up to date)."
 
-    so = HERE / 'libms_oracle.so'
-    src = [HERE / 'ms_oracle.c', HERE / 'ms_oracle.h']
-
-    # content hash, not file times: those do not survive the copy to the GPU box in any useful order
-    import hashlib
-    digest = hashlib.sha256(b''.join(s.read_bytes() for s in src + [HERE / 'Makefile'] if s.exists())).hexdigest()
-    stamp = HERE / 'libms_oracle.so.stamp'
-
-    if force or not so.exists() or not stamp.exists() or stamp.read_text().strip() != digest:
+    if force or stale():
         subprocess.run(['make', '-B', '-C', str(HERE), 'libms_oracle.so'], check=True, capture_output=True)
-        stamp.write_text(digest)
+        (HERE / 'libms_oracle.so.stamp').write_text(_digest())
 
-    return so
+    return HERE / 'libms_oracle.so'
 
 
 def lib():

@@ -2,7 +2,7 @@
 # TEST-ONLY gate: the compilers' own analysis of reads before writes over every kernel family of the device header (host emulation units).
 #   g++   -O2 -Werror=uninitialized -Werror=maybe-uninitialized      (data-flow analysis after inlining: what named Solver::evs in round 5)
 #   clang -Werror=uninitialized -Werror=sometimes-uninitialized -Werror=conditional-uninitialized      (ROCm's clang, the device compiler's front end)
-# Exit code 0: no finding.  Twenty minutes of CPU (g++ -O2 on the fused kernels); opt-in from pytest: RUN_SANITIZERS=1 ... -k uninitialized
+# Exit code 0: no finding.  Thirty minutes of CPU (g++ -O2 on the fused kernels), the units side by side; from pytest: -k uninitialized (part of every run)
 cd "$(dirname "$0")"
 OBJ=${OBJDIR:-/tmp/msd_emu_warn_obj}
 CLANGXX=${CLANGXX:-/opt/rocm/lib/llvm/bin/clang++}

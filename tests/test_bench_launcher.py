@@ -167,3 +167,43 @@ def test_roofline_block_fields():
     assert abs(r['achieved'] - 904*100*1024*20.6/1.15e-3/1e9) < 1e-6*r['achieved'] and abs(r['frac'] - r['achieved']/8000.0) < 1e-12
     assert r['traffic'] is None and r['frac_measured'] is None
     assert abs(r['compulsory_bytes_per_launch'] - 1024*(8*502 + 168)) < 1e-9
+
+
+def test_full_and_dump_options(tmp_path):
+    "the legs that take runs of their own are off unless --full asks for them; --dump-outputs names a directory and the arrays land there as float64"
+    import numpy as np
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    b = bench.parse_args(['--full', '--dump-outputs', str(tmp_path / 'out'), '--steps', '7'])
+    assert b.full is True and b.dump_outputs == str(tmp_path / 'out') and b.steps == 7
+    bench.dump_outputs(b.dump_outputs, {"status": np.arange(4, dtype=np.int32), "z": np.ones((4, 3), dtype=np.float32)}, 0, 1)
+    bench.dump_outputs(b.dump_outputs, {"status": np.zeros(2)}, 3, 8)
+    assert sorted(p.name for p in (tmp_path / 'out').iterdir()) == ['status.npy', 'status_rank3.npy', 'z.npy']
+    z = np.load(tmp_path / 'out' / 'z.npy')
+    assert z.dtype == np.float64 and z.shape == (4, 3) and np.load(tmp_path / 'out' / 'status.npy').tolist() == [0.0, 1.0, 2.0, 3.0]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_it_solved(tmp_path):
+    """
+    A plain run prints the headline line without the legs of --full, takes the number of timed steps from --steps, and --dump-outputs writes
+    the solutions of the last timed step: the same arrays from two runs with the same arguments (seeded scenarios; the kernels repeat launch to
+    launch, test_follow_up_kernels_are_deterministic_launch_to_launch, so the bound is rounding noise of double precision, 1e-12).
+    """
+    import numpy as np
+    lines, outs = [], []
+    for k in range(2):
+        d = tmp_path / ('run%d' % k)
+        out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1', '--no-build', '--dump-outputs', str(d)],
+                             env=_clean_env(), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1]))
+        outs.append({p.stem: np.load(p) for p in sorted(d.glob('*.npy'))})
+    line = lines[0]
+    assert 'alt' not in line and 'cpu_baseline' not in line and line['steps'] == 4 and line['config']['converged'] == 1024
+    assert line['value'] == pytest.approx(4*1024/(4*line['ms_per_step']*1e-3))
+    assert set(outs[0]) == {'z', 'cost', 'status', 'iterations'}
+    assert outs[0]['z'].dtype == np.float64 and outs[0]['z'].shape[0] == 1024 and outs[0]['cost'].shape == (1024,)
+    assert np.all(outs[0]['status'] >= 0) and np.mean(outs[0]['iterations']) == pytest.approx(line['config']['ip_iterations_mean'])
+    for name in outs[0]:
+        assert np.allclose(outs[0][name], outs[1][name], rtol=1e-12, atol=1e-12), name

@@ -6,6 +6,7 @@ can only be seen on the GPU (tests/test_gpu_parity.py).  Emulation is test tooli
 """
 
 import ctypes
+import os
 import subprocess
 from pathlib import Path
 
@@ -423,8 +424,10 @@ def test_emulation_under_memory_sanitizer():
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
 
 
-@pytest.mark.skipif(not __import__('os').environ.get('RUN_SANITIZERS'), reason="opt-in (twenty minutes of CPU): RUN_SANITIZERS=1")
-def test_compilers_name_no_uninitialized_read_in_the_device_header():
-    "g++ -O2 -Werror=maybe-uninitialized and clang -Werror=sometimes/conditional-uninitialized over every emulation unit: tests/hip_emu/check_uninitialized.sh"
-    r = subprocess.run([str(EMU / 'check_uninitialized.sh')], capture_output=True, text=True, timeout=2*3600)
+def test_compilers_name_no_uninitialized_read_in_the_device_header(tmp_path):
+    """
+    g++ -O2 -Werror=maybe-uninitialized and clang -Werror=sometimes/conditional-uninitialized over every emulation unit: tests/hip_emu/check_uninitialized.sh.
+    Part of every run (compile only: thirty minutes of CPU, the units side by side), its objects and logs in the test's own directory.
+    """
+    r = subprocess.run([str(EMU / 'check_uninitialized.sh')], env=dict(os.environ, OBJDIR=str(tmp_path)), capture_output=True, text=True, timeout=2*3600)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])

@@ -10,7 +10,7 @@ mkdir -p $out
 cd $repo
 python3 __graft_entry__.py > $out/build.log 2>&1            # un-profiled: the compiler never runs under the profiler's preload
 if [ $? -ne 0 ]; then echo "profile_round: the build failed (see $out/build.log): nothing is measured"; tail -5 $out/build.log; exit 1; fi
-python3 bench.py --no-build > $out/bench.json 2> $out/bench.err || { echo "profile_round: bench.py failed"; tail -5 $out/bench.err; exit 1; }
+python3 bench.py --no-build --full > $out/bench.json 2> $out/bench.err || { echo "profile_round: bench.py failed"; tail -5 $out/bench.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 P="--no-build --no-cpu-baseline --no-alt"
 if [ "$2" = quick ]; then LIST="c1:"; else
@@ -35,5 +35,5 @@ if [ $traffic_rc -eq 0 ] && python3 -c "import json, sys; d = json.load(open(sys
 else
   echo "profile_round: make_traffic_json.py failed (rc $traffic_rc) or wrote no valid JSON: profiles/hbm_traffic.json is left as it was"; tail -5 $out/hbm_traffic.err
 fi
-python3 bench.py --no-build > $out/bench_with_traffic.json 2> $out/bench_with_traffic.err
+python3 bench.py --no-build --full > $out/bench_with_traffic.json 2> $out/bench_with_traffic.err
 cat $out/summary.txt
