@@ -45,6 +45,14 @@ int msd_problem_direct_results(msd_handle h, int on);
 int msd_tuning(const char *name, int value);
 
 /*
+ * The launch plan the library selects for a description, as one line of text in buf (len bytes): family, structure, NT SPT lds_bytes stream fused_family
+ * work_doubles nz nl, NT2 SPT2 lds_bytes2 and the symbol names of the first-pass kernel, the least-squares first pass, the follow-up kernel and the candidate
+ * with the second-order correction inside ("-": none; whether the candidate is taken depends on the device's occupancy).  Makes no device call.  A
+ * description msd_problem_create would reject gets the same code and msd_last_error() here (tests/test_abi.py pins the table).
+ */
+int msd_plan_describe(const msd_problem_desc *desc, char *buf, int len);
+
+/*
  * Test hook: the reciprocal and the square root / reciprocal square root of the fused interior-point iteration (csrc/msd_fastmath.hpp: v_rcp_f64 /
  * v_rsq_f64 refined without the compiler's range scaling) evaluated on n operands, so that the GPU tests can bound their error against the IEEE
  * operations (tests/test_gpu_parity.py::test_fast_reciprocal_and_square_root: <= 1 ulp on normal operands).  Errors: msd_interval_last_error().

@@ -7,6 +7,7 @@
  * (workgroups stride through the batch), dynamic LDS = lds_doubles(N, NT) * 8 bytes.
  */
 #include <hip/hip_runtime.h>
+#include <dlfcn.h>
 
 #include <algorithm>
 #include <cmath>
@@ -33,12 +34,6 @@ namespace msd_host {
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
 }
 using msd_host::fail;
-
-namespace msd {
-/* (msd_kernels_stream4.hip; declared here and not in msd_geometry.hpp, which every kernel unit depends on) */
-Geometry pick_stream_geometry_general_dynamic(int N);
-Geometry pick_stream_geometry_general_intloss(int N);
-}
 
 namespace msd_host {
 
@@ -117,34 +112,57 @@ static int kernel_limits(int device, const void *fn, int threads, size_t lds, in
 }
 
 
-/* kernel geometry of a problem's horizon and structure, resident workgroups, problem record without the profile pointers */
-int make_plan(int device, const msd_problem_desc *d, Plan *out)
+/* the LDS-resident kernels of a family.  The pickers take the structure their family has kernels for: general / intloss the one with both brakes (a
+ * bool), dynamic the two of the energy problem, static every one */
+msd::Geometry pick_resident(Family family, int N, int structure)
+{
+    const bool full = structure == msd::FULL_BOTH;
+    switch (family) {
+    case INTLOSS_TABLE: return msd::pick_geometry_intloss_table(N);
+    case GENERAL_DYNAMIC: return msd::pick_geometry_general_dynamic(N);
+    case GENERAL_INTLOSS: return msd::pick_geometry_general_intloss(N);
+    case GENERAL: return msd::pick_geometry_general(N, full);
+    case INTLOSS: return msd::pick_geometry_intloss(N, full);
+    case DYNAMIC: return msd::pick_geometry_dynamic(N, (full || structure == msd::FULL_RG) ? structure : 0);
+    case STATIC: return msd::pick_geometry_static(N, structure);
+    }
+    return {0, 0, nullptr};
+}
+
+/* the streamed kernels of a family (stage blocks in device memory): first pass + follow-up kernel.  Only the static family has first passes with a
+ * structure compiled in, the two of the energy problem */
+msd::Geometry pick_streamed(Family family, int N, int structure)
+{
+    switch (family) {
+    case INTLOSS_TABLE: return msd::pick_stream_geometry_intloss_table(N);
+    case GENERAL_DYNAMIC: return msd::pick_stream_geometry_general_dynamic(N);
+    case GENERAL_INTLOSS: return msd::pick_stream_geometry_general_intloss(N);
+    case GENERAL: return msd::pick_stream_geometry_general(N);
+    case INTLOSS: return msd::pick_stream_geometry_intloss(N);
+    case DYNAMIC: return msd::pick_stream_geometry_dynamic(N);
+    case STATIC: return msd::pick_stream_geometry_static(N, (structure == msd::FULL_BOTH || structure == msd::FULL_RG) ? structure : 0);
+    }
+    return {0, 0, nullptr};
+}
+
+/* kernel geometry of a problem's horizon and structure, problem record without the profile pointers: everything of a plan that needs no device
+ * (geo_out: the geometry picked, with the follow-up kernel the plan takes) */
+int select_plan(const msd_problem_desc *d, Plan *out, msd::Geometry *geo_out)
 {
     Plan &pl = *out;
     const int N = d->num_intervals;
-    const bool dyn = d->loss_kind == 2;
-    const bool gen = d->integrator != 0, intloss = d->integrate_losses != 0 && d->energy_optimal != 0;
-    const bool wide = dyn || intloss;      /* stage blocks with the slack-b and slack-Fpb couplings */
-    const bool itab = dyn && intloss;      /* the loss table integrated over the running time (msd_lossint_table.hpp: DYN = LOSS_INTEGRATED_TABLE) */
-    /* both brakes, power rows (finite by construction: ocp.py:186-187), energy objective, finite acceleration bounds (ocp.py:113-114) */
-    const bool full = d->with_pn_brake != 0 && d->has_power_rows != 0 && d->energy_optimal != 0 && std::isfinite(d->acc_min) && std::isfinite(d->acc_max)
-                      && std::isfinite(d->pw_upper) && std::isfinite(d->pw_lower);
-    /* the same without the pneumatic brake (forceMinPn = 0: the reference's scripts); static loss rows + explicit Runge-Kutta shooting only */
-    const bool full_rg = d->with_pn_brake == 0 && d->has_power_rows != 0 && d->energy_optimal != 0 && std::isfinite(d->acc_min) && std::isfinite(d->acc_max)
-                         && std::isfinite(d->pw_upper) && std::isfinite(d->pw_lower);
-    /* the time-optimal problem on the same rolling stock (energyOptimal = False: minimumTime, the twins of msd_mpc.hip): power rows and acceleration row, no loss rows */
-    const bool full_time = d->energy_optimal == 0 && d->has_power_rows != 0 && std::isfinite(d->acc_min) && std::isfinite(d->acc_max) && std::isfinite(d->pw_upper) && std::isfinite(d->pw_lower);
-    const int structure = full ? msd::FULL_BOTH : full_rg ? msd::FULL_RG : full_time ? (d->with_pn_brake != 0 ? msd::FULL_TIME_BOTH : msd::FULL_TIME_RG) : 0;
-    msd::Geometry geo = itab ? msd::pick_geometry_intloss_table(N) : (gen && dyn) ? msd::pick_geometry_general_dynamic(N) : (gen && intloss) ? msd::pick_geometry_general_intloss(N) : gen ? msd::pick_geometry_general(N, full) : intloss ? msd::pick_geometry_intloss(N, full)
-                        : dyn ? msd::pick_geometry_dynamic(N, full ? msd::FULL_BOTH : full_rg ? msd::FULL_RG : 0) : msd::pick_geometry_static(N, structure);
+    const Family family = family_of(d);
+    const int structure = structure_of(d);
+    const bool gen = d->integrator != 0;
+    const bool wide = d->loss_kind == 2 || (d->integrate_losses != 0 && d->energy_optimal != 0);      /* stage blocks with the slack-b and slack-Fpb couplings */
+    msd::Geometry geo = pick_resident(family, N, structure);
     size_t lds = geo.fn ? sizeof(double)*(size_t)(msd::lds_doubles(N, geo.NT*geo.SPT, wide, geo.xch, geo.red) + msd::coop_doubles(geo.NT, gen) + geo.extra) : 0;
     if (!geo.fn || lds > 160*1024) {
         /* the stage blocks do not fit the LDS of a compute unit: the streamed kernels keep them in device memory */
-        geo = itab ? msd::pick_stream_geometry_intloss_table(N) : (gen && dyn) ? msd::pick_stream_geometry_general_dynamic(N) : (gen && intloss) ? msd::pick_stream_geometry_general_intloss(N) : gen ? msd::pick_stream_geometry_general(N) : intloss ? msd::pick_stream_geometry_intloss(N)
-              : dyn ? msd::pick_stream_geometry_dynamic(N) : msd::pick_stream_geometry_static(N, full ? msd::FULL_BOTH : full_rg ? msd::FULL_RG : 0);
+        geo = pick_streamed(family, N, structure);
         lds = sizeof(double)*(size_t)msd::lds_doubles_stream();
         if (!geo.fn)
-            return fail(MSD_E_UNSUPPORTED, (gen || intloss || dyn) ? "numIntervals = " + std::to_string(N) + " exceeds the 1023 intervals of the streamed kernels for the dynamic loss model, the collocation / adaptive shooting integrators and integrateLosses"
+            return fail(MSD_E_UNSUPPORTED, family != STATIC ? "numIntervals = " + std::to_string(N) + " exceeds the 1023 intervals of the streamed kernels for the dynamic loss model, the collocation / adaptive shooting integrators and integrateLosses"
                                            : "numIntervals = " + std::to_string(N) + " exceeds the 5119 intervals of the streamed kernel");
     }
     pl.NT = geo.NT; pl.SPT = geo.SPT; pl.lds_bytes = lds; pl.stream = geo.stream;
@@ -164,19 +182,12 @@ int make_plan(int device, const msd_problem_desc *d, Plan *out)
     P.wdTrigger = d->watchdog_trigger == 0 ? 10 : d->watchdog_trigger;      /* IPOPT's default */
     if (d->integrator == MSD_INTEGRATOR_ADAPTIVE) P.numApprox = 0;      /* train.py:314 */
 
-    int per_cu = 0, cus = 0;
-    int rc = kernel_limits(device, (const void *)geo.fn, geo.NT, lds, &per_cu);
-    if (rc != MSD_OK) return rc;
-    rc = cu_count(device, &cus);
-    if (rc != MSD_OK) return rc;
-    pl.max_grid = per_cu*cus;
-    pl.max_grid2 = 0;
     pl.NT2 = geo.NT; pl.SPT2 = geo.SPT; pl.lds_bytes2 = lds;
-    if (geo.fn2 && geo.NT == 64 && geo.SPT == 1 && geo.xch == msd::XCH_FAST && full) {
+    if (geo.fn2 && geo.NT == 64 && geo.SPT == 1 && geo.xch == msd::XCH_FAST && structure == msd::FULL_BOTH) {
         /* horizons of up to 63 intervals, both brakes: the first pass runs one node per lane, the follow-up kernel is the two-nodes-per-lane one (its second
          * node slots stay idle; the follow-up kernel restarts a scenario from its starting point, so nothing ties its geometry to the first pass's -- and the
          * family has no 64 x 1 follow-up instantiation).  The one-brake family has its 64 x 1 follow-up kernel back (round 6: msd_kernels_rg2.hip) */
-        geo.fn2 = full ? msd::follow_kernel_full(64, 2) : msd::follow_kernel_full_rg(64, 2);
+        geo.fn2 = msd::follow_kernel_full(64, 2);
         pl.NT2 = 64; pl.SPT2 = 2;
         pl.lds_bytes2 = sizeof(double)*(size_t)msd::lds_doubles(N, 128, wide, geo.xch, geo.red);
     }
@@ -185,36 +196,87 @@ int make_plan(int device, const msd_problem_desc *d, Plan *out)
         /* an LDS-resident kernel without a follow-up kernel of its own geometry (every family but the two with the structure of the reference's rolling
          * stock compiled in): a first-pass kernel -- the general iteration without the restoration phase and the watchdog procedure; a scenario that needs
          * either is followed up by the streamed kernel of the family (msd_kernel.hpp: FAMILY_HAS_RESTO, WD_HANDOVER).  The follow-up restarts the
-         * scenario, so the two geometries need not agree */
-        const msd::Geometry g2 = itab ? msd::pick_stream_geometry_intloss_table(N) : (gen && dyn) ? msd::pick_stream_geometry_general_dynamic(N) : (gen && intloss) ? msd::pick_stream_geometry_general_intloss(N) : gen ? msd::pick_stream_geometry_general(N)
-                                 : intloss ? msd::pick_stream_geometry_intloss(N) : dyn ? msd::pick_stream_geometry_dynamic(N) : msd::pick_stream_geometry_static(N);
+         * scenario, so the two geometries need not agree; and the structure does not matter here: it selects the streamed first pass only, the
+         * streamed follow-up kernel is the general one whatever the structure */
+        const msd::Geometry g2 = pick_streamed(family, N, structure);
         if (!g2.fn2) return fail(MSD_E_UNSUPPORTED, "no follow-up kernel for numIntervals = " + std::to_string(N));
         geo.fn2 = g2.fn2; pl.NT2 = g2.NT; pl.SPT2 = g2.SPT;
         pl.lds_bytes2 = sizeof(double)*(size_t)msd::lds_doubles_stream();
         work2 = msd::stream_doubles(N, g2.NT*g2.SPT, wide);
-    }
-    if (geo.fn2) {
-        rc = kernel_limits(device, (const void *)geo.fn2, pl.NT2, pl.lds_bytes2, &per_cu);
-        if (rc != MSD_OK) return rc;
-        pl.max_grid2 = per_cu*cus;
-    }
-    pl.max_grid_lsq = 0;
-    if (geo.fn_lsq) {
-        rc = kernel_limits(device, (const void *)geo.fn_lsq, geo.NT, lds, &per_cu);
-        if (rc != MSD_OK) return rc;
-        pl.max_grid_lsq = per_cu*cus;
     }
     pl.fused_family = geo.fn2 != nullptr && geo.xch == msd::XCH_FAST;
     pl.work_doubles = geo.stream ? msd::stream_doubles(N, geo.NT*geo.SPT, wide) : std::max(work2, msd::work_doubles(std::max(geo.NT*geo.SPT, work2 ? 0 : pl.NT2*pl.SPT2)));
     pl.nz = (4 + P.withPn)*N + 2; pl.nl = ((P.hasPower ? 2 : 0) + 3 + (P.energyOpt ? 2 : 0))*N;
     pl.kernel = geo.fn; pl.kernel2 = geo.fn2; pl.kernel_lsq = geo.fn_lsq;
     pl.kernel_soc = nullptr;
+    *geo_out = geo;
+    return MSD_OK;
+}
+
+/* select_plan + what the device says: the resident workgroups of the plan's kernels, and whether the second-order-correction kernel is taken */
+int make_plan(int device, const msd_problem_desc *d, Plan *out)
+{
+    Plan &pl = *out;
+    msd::Geometry geo{0, 0, nullptr};
+    int rc = select_plan(d, &pl, &geo);
+    if (rc != MSD_OK) return rc;
+    int per_cu = 0, cus = 0;
+    rc = kernel_limits(device, (const void *)pl.kernel, pl.NT, pl.lds_bytes, &per_cu);
+    if (rc != MSD_OK) return rc;
+    rc = cu_count(device, &cus);
+    if (rc != MSD_OK) return rc;
+    pl.max_grid = per_cu*cus;
+    pl.max_grid2 = 0;
+    if (pl.kernel2) {
+        rc = kernel_limits(device, (const void *)pl.kernel2, pl.NT2, pl.lds_bytes2, &per_cu);
+        if (rc != MSD_OK) return rc;
+        pl.max_grid2 = per_cu*cus;
+    }
+    pl.max_grid_lsq = 0;
+    if (pl.kernel_lsq) {
+        rc = kernel_limits(device, (const void *)pl.kernel_lsq, pl.NT, pl.lds_bytes, &per_cu);
+        if (rc != MSD_OK) return rc;
+        pl.max_grid_lsq = per_cu*cus;
+    }
     if (geo.fn_soc) {
         /* (same launch as `kernel`; taken only when it is as resident) */
         int per_cu_soc = 0;
-        if (kernel_limits(device, (const void *)geo.fn_soc, geo.NT, lds, &per_cu_soc) == MSD_OK && per_cu_soc*cus >= pl.max_grid) pl.kernel_soc = geo.fn_soc;
+        if (kernel_limits(device, (const void *)geo.fn_soc, pl.NT, pl.lds_bytes, &per_cu_soc) == MSD_OK && per_cu_soc*cus >= pl.max_grid) pl.kernel_soc = geo.fn_soc;
     }
     return MSD_OK;
+}
+
+void pack_profile(const msd_problem_desc *d, double *out)
+{
+    const int N = d->num_intervals;
+    double *ds = out, *grad = ds + N, *curv = grad + N, *bmax = curv + N, *pos = bmax + N + 1;
+    memcpy(ds, d->ds, sizeof(double)*N); memcpy(grad, d->grad, sizeof(double)*N); memcpy(curv, d->curv, sizeof(double)*N);
+    memcpy(bmax, d->bmax, sizeof(double)*(N + 1));
+    pos[0] = 0;
+    for (int i = 0; i < N; i++) pos[i + 1] = pos[i] + d->ds[i];
+}
+
+/* the exported symbol a kernel pointer is the address of */
+static std::string kernel_name(msd::KernelFn fn)
+{
+    if (!fn) return "-";
+    static std::mutex mu;
+    static std::map<const void *, std::string> cache;      /* (dladdr walks the library's symbol table) */
+    std::lock_guard<std::mutex> lock(mu);
+    std::string &name = cache[(const void *)fn];
+    if (name.empty()) {
+        Dl_info info;
+        name = (dladdr((const void *)fn, &info) && info.dli_sname && info.dli_saddr == (const void *)fn) ? info.dli_sname : "?";
+    }
+    return name;
+}
+
+std::string plan_text(const Plan &pl, msd::KernelFn soc)
+{
+    char buf[256];
+    snprintf(buf, sizeof buf, "NT=%d SPT=%d lds_bytes=%zu stream=%d fused_family=%d work_doubles=%zu nz=%d nl=%d NT2=%d SPT2=%d lds_bytes2=%zu", pl.NT, pl.SPT, pl.lds_bytes,
+             (int)pl.stream, (int)pl.fused_family, pl.work_doubles, pl.nz, pl.nl, pl.NT2, pl.SPT2, pl.lds_bytes2);
+    return std::string(buf) + " kernel=" + kernel_name(pl.kernel) + " kernel_lsq=" + kernel_name(pl.kernel_lsq) + " kernel2=" + kernel_name(pl.kernel2) + " kernel_soc=" + kernel_name(soc);
 }
 
 int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follow, int *d_queue, int nscen, const double *d_scen, const double *d_ovr,
@@ -295,6 +357,23 @@ int msd_tuning(const char *name, int value)
     return MSD_OK;
 }
 
+int msd_plan_describe(const msd_problem_desc *d, char *buf, int len)
+{
+    if (!d || !buf || len < 1) return fail(MSD_E_INVALID, "null argument");
+    int rc = check_desc(d);
+    if (rc != MSD_OK) return rc;
+    msd_host::Plan pl;
+    msd::Geometry geo{0, 0, nullptr};
+    rc = msd_host::select_plan(d, &pl, &geo);
+    if (rc != MSD_OK) return rc;
+    static const char *const family[] = {"STATIC", "DYNAMIC", "INTLOSS", "INTLOSS_TABLE", "GENERAL", "GENERAL_DYNAMIC", "GENERAL_INTLOSS"};
+    static const char *const structure[] = {"0", "FULL_BOTH", "FULL_RG", "FULL_TIME_BOTH", "FULL_TIME_RG"};
+    const std::string line = std::string("family=") + family[msd_host::family_of(d)] + " structure=" + structure[msd_host::structure_of(d)] + " " + msd_host::plan_text(pl, geo.fn_soc);
+    if ((int)line.size() >= len) return fail(MSD_E_INVALID, "msd_plan_describe: the line needs " + std::to_string(line.size() + 1) + " bytes");
+    memcpy(buf, line.c_str(), line.size() + 1);
+    return MSD_OK;
+}
+
 int msd_device_count(void)
 {
     int n = 0;
@@ -314,32 +393,25 @@ static int configure(msd_problem *h, const msd_problem_desc *d)
     if (rc != MSD_OK) return rc;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));      /* nothing of the previous problem may still be running */
-    h->kernel = nullptr;                           /* the handle holds no problem until every step below has succeeded (launch() checks) */
+    h->plan.kernel = nullptr;                      /* the handle holds no problem until every step below has succeeded (launch() checks) */
 
-    /* ds | grad | curv | bmax | pos in one buffer */
+    const size_t len = msd_host::profile_doubles(N);      /* ds | grad | curv | bmax | pos in one buffer */
     if (N > h->cap_N) {
         hipFree(h->d_prof); h->d_prof = nullptr; h->cap_N = 0;
-        HIP_TRY(hipMalloc((void **)&h->d_prof, sizeof(double)*(5*(size_t)N + 2)));
+        HIP_TRY(hipMalloc((void **)&h->d_prof, sizeof(double)*len));
         h->cap_N = N;
     }
-    {
-        /* through a pinned staging buffer of the handle, on the handle's stream: the launches that follow are ordered behind the copy and
-         * nothing waits here (a synchronous copy from pageable memory costs most of a millisecond per re-solve of a receding horizon);
-         * the stream was synchronised above, so the buffer is free */
-        const size_t len = 5*(size_t)N + 2;
-        if (len > h->cap_stage) {
-            if (h->h_stage) hipHostFree(h->h_stage);
-            h->h_stage = nullptr; h->cap_stage = 0;
-            HIP_TRY(hipHostMalloc((void **)&h->h_stage, sizeof(double)*len, hipHostMallocDefault));
-            h->cap_stage = len;
-        }
-        double *ds = h->h_stage, *grad = ds + N, *curv = grad + N, *bmax = curv + N, *pos = bmax + N + 1;
-        memcpy(ds, d->ds, sizeof(double)*N); memcpy(grad, d->grad, sizeof(double)*N); memcpy(curv, d->curv, sizeof(double)*N);
-        memcpy(bmax, d->bmax, sizeof(double)*(N + 1));
-        pos[0] = 0;
-        for (int i = 0; i < N; i++) pos[i + 1] = pos[i] + d->ds[i];
-        HIP_TRY(hipMemcpyAsync(h->d_prof, h->h_stage, sizeof(double)*len, hipMemcpyHostToDevice, h->stream));
+    /* through a pinned staging buffer of the handle, on the handle's stream: the launches that follow are ordered behind the copy and
+     * nothing waits here (a synchronous copy from pageable memory costs most of a millisecond per re-solve of a receding horizon);
+     * the stream was synchronised above, so the buffer is free */
+    if (len > h->cap_stage) {
+        if (h->h_stage) hipHostFree(h->h_stage);
+        h->h_stage = nullptr; h->cap_stage = 0;
+        HIP_TRY(hipHostMalloc((void **)&h->h_stage, sizeof(double)*len, hipHostMallocDefault));
+        h->cap_stage = len;
     }
+    msd_host::pack_profile(d, h->h_stage);
+    HIP_TRY(hipMemcpyAsync(h->d_prof, h->h_stage, sizeof(double)*len, hipMemcpyHostToDevice, h->stream));
     if (d->loss_kind == 2) {
         if (d->loss_table_len > h->cap_loss) {
             hipFree(h->d_loss); h->d_loss = nullptr; h->cap_loss = 0;
@@ -355,38 +427,28 @@ static int configure(msd_problem *h, const msd_problem_desc *d)
         HIP_TRY(hipMemcpy(h->d_coll, d->coll_tables, sizeof(double)*len, hipMemcpyHostToDevice));
     }
 
-    h->NT = pl.NT; h->SPT = pl.SPT; h->lds_bytes = pl.lds_bytes; h->stream_kernel = pl.stream;
-    h->P = pl.P;
-    msd::DevProb &P = h->P;
-    P.ds = h->d_prof; P.grad = P.ds + N; P.curv = P.grad + N; P.bmax = P.curv + N; P.pos = P.bmax + N + 1;
-    P.loss = (d->loss_kind == 2) ? h->d_loss : nullptr;
-    P.coll = (d->integrator == MSD_INTEGRATOR_COLLOCATION) ? h->d_coll : nullptr;
-    h->max_grid = pl.max_grid; h->max_grid2 = pl.max_grid2; h->max_grid_lsq = pl.max_grid_lsq; h->fused_family = pl.fused_family;
-    h->NT2 = pl.NT2; h->SPT2 = pl.SPT2; h->lds_bytes2 = pl.lds_bytes2;
-    h->work_per_wg = pl.work_doubles;
-    {
-        const size_t need = pl.work_doubles*(size_t)std::max(h->max_grid, std::max(h->max_grid2, h->max_grid_lsq));
-        if (need > h->cap_work) {
-            hipFree(h->d_work); h->d_work = nullptr; h->cap_work = 0;
-            HIP_TRY(hipMalloc((void **)&h->d_work, sizeof(double)*need));
-            h->cap_work = need;
-        }
+    msd_host::point_profile(pl.P, h->d_prof);
+    pl.P.loss = (d->loss_kind == 2) ? h->d_loss : nullptr;
+    pl.P.coll = (d->integrator == MSD_INTEGRATOR_COLLOCATION) ? h->d_coll : nullptr;
+    if (pl.work_area() > h->cap_work) {
+        hipFree(h->d_work); h->d_work = nullptr; h->cap_work = 0;
+        HIP_TRY(hipMalloc((void **)&h->d_work, sizeof(double)*pl.work_area()));
+        h->cap_work = pl.work_area();
     }
     /* the scenario buffers are sized by nz: a different layout invalidates them */
-    const int nz = (4 + P.withPn)*N + 2, nl = ((P.hasPower ? 2 : 0) + 3 + (P.energyOpt ? 2 : 0))*N;
-    if (nz > h->cap_nz || nl > h->cap_nl) {
+    if (pl.nz > h->cap_nz || pl.nl > h->cap_nl) {
         hipFree(h->d_scen); hipFree(h->d_ovr); hipFree(h->d_z); hipFree(h->d_lam); hipFree(h->d_stats); hipFree(h->d_guess); hipFree(h->d_z2); hipFree(h->d_stats2);
         h->d_scen = h->d_ovr = h->d_z = h->d_lam = h->d_stats = h->d_guess = h->d_z2 = h->d_stats2 = nullptr; h->cap_scen = 0; h->cap_guess = 0;
         h->prev_nscen = 0;
-        h->cap_nz = nz; h->cap_nl = nl;
+        h->cap_nz = pl.nz; h->cap_nl = pl.nl;
     }
-    h->kernel = pl.kernel; h->kernel2 = pl.kernel2; h->kernel_lsq = pl.kernel_lsq; h->kernel_soc = pl.kernel_soc;
-    if (h->kernel_soc && !h->h_soc_seen) {
+    if (pl.kernel_soc && !h->h_soc_seen) {
         /* one word of page-locked host memory the kernels can write: "a launch of this handle handed a second-order correction over" */
         HIP_TRY(hipHostMalloc((void **)&h->h_soc_seen, sizeof(int), hipHostMallocMapped));
         HIP_TRY(hipHostGetDevicePointer((void **)&h->d_soc_seen, (void *)h->h_soc_seen, 0));
     }
     if (h->h_soc_seen) *h->h_soc_seen = 0;      /* (another problem: the verdict starts afresh; the stream was synchronised above) */
+    h->plan = pl;
     return MSD_OK;
 }
 
@@ -414,9 +476,12 @@ int msd_problem_create(const msd_problem_desc *d, int device, msd_handle *out)
 int msd_problem_reconfigure(msd_handle h, const msd_problem_desc *d)
 {
     if (!h || !d) return fail(MSD_E_INVALID, "null argument");
+    /* Whatever rejects the description or fails on the way (check_desc, the selection of a plan, a HIP call), the handle holds no problem afterwards:
+     * its solves fail with "the handle holds no problem" until a reconfiguration succeeds.  Stream, events and buffers are kept */
     int rc = check_desc(d);
-    if (rc != MSD_OK) return rc;
-    return configure(h, d);
+    if (rc == MSD_OK) rc = configure(h, d);
+    if (rc != MSD_OK) h->plan.kernel = nullptr;
+    return rc;
 }
 
 int msd_problem_destroy(msd_handle h)
@@ -437,39 +502,29 @@ int msd_problem_destroy(msd_handle h)
     return MSD_OK;
 }
 
-int msd_problem_nz(msd_handle h) { return h ? (4 + h->P.withPn)*h->P.N + 2 : 0; }
-int msd_problem_rows_per_interval(msd_handle h) { return h ? (h->P.hasPower ? 2 : 0) + 3 + (h->P.energyOpt ? 2 : 0) : 0; }
+int msd_problem_nz(msd_handle h) { return h ? h->plan.nz : 0; }
+/* (P.N >= 1: a handle exists only after a successful configure(), and a failed reconfiguration clears plan.kernel alone) */
+int msd_problem_rows_per_interval(msd_handle h) { return h ? h->plan.nl/h->plan.P.N : 0; }
 
 constexpr int QUEUE_RING = 64;
 
 using msd_host::WarmStart;
 
-/* the launch plan a configured handle holds */
-static msd_host::Plan plan_of(const msd_problem *h)
-{
-    msd_host::Plan pl;
-    pl.P = h->P; pl.NT = h->NT; pl.SPT = h->SPT; pl.lds_bytes = h->lds_bytes; pl.stream = h->stream_kernel;
-    pl.kernel = h->kernel; pl.kernel_lsq = h->kernel_lsq; pl.kernel2 = h->kernel2; pl.kernel_soc = h->kernel_soc; pl.NT2 = h->NT2; pl.SPT2 = h->SPT2; pl.lds_bytes2 = h->lds_bytes2;
-    pl.max_grid = h->max_grid; pl.max_grid_lsq = h->max_grid_lsq; pl.max_grid2 = h->max_grid2; pl.fused_family = h->fused_family;
-    pl.work_doubles = h->work_per_wg; pl.nz = msd_problem_nz(const_cast<msd_problem *>(h)); pl.nl = msd_problem_rows_per_interval(const_cast<msd_problem *>(h))*h->P.N;
-    return pl;
-}
-
 static int launch(msd_handle h, int nscen, const double *d_scen, const double *d_ovr, double *d_z, double *d_lam, double *d_stats, double *d_hist, int hist_cap,
                   const WarmStart &ws_in = WarmStart())
 {
-    if (!h->kernel) return fail(MSD_E_INVALID, "the handle holds no problem: its last (re)configuration failed");
+    if (!h->plan.kernel) return fail(MSD_E_INVALID, "the handle holds no problem: its last (re)configuration failed");
     /* Second-order corrections (IPOPT's default behaviour, ocp.py:290): the first-pass kernel of the benchmark geometries hands a scenario that needs one to
      * the follow-up kernel, whose general iteration solves it again from its starting point -- one such scenario is the tail of its launch (config 3: 1.3 ms
      * behind a 6.3 ms first pass).  A handle whose launches have met one takes the first-pass kernel with the correction inside the fused iteration from
      * then on (msd_kernel.hpp: SOCK; 4 % slower per iteration, no tail); the kernels report it through a word of mapped host memory, read here without
      * waiting for anything */
     WarmStart ws = ws_in;
-    if (h->kernel_soc) {
+    if (h->plan.kernel_soc) {
         ws.d_soc_seen = h->d_soc_seen;
         if (*h->h_soc_seen != 0) ws.use_soc = true;
     }
-    if (h->kernel2) {
+    if (h->plan.kernel2) {
         const size_t need = msd::FOLLOW_HDR + 2*(size_t)nscen;
         if (need > h->cap_follow) {
             HIP_TRY(hipStreamSynchronize(h->stream));      /* (a follow-up kernel in flight reads the old list) */
@@ -496,11 +551,11 @@ static int launch(msd_handle h, int nscen, const double *d_scen, const double *d
     }
 #ifdef MSD_DEBUG_HOOKS      /* (diagnostic builds: the device buffers of a launch, to place the address of a memory fault) */
     if (getenv("MSD_DEBUG_PTRS"))
-        fprintf(stderr, "[msd] launch nscen %d  work %p (+%zu B)  follow %p  queue %p  prof %p  scen %p  z %p  lam %p  stats %p  hist %p  NT %d SPT %d NT2 %d SPT2 %d lds %zu lds2 %zu grid caps %d %d %d\n",
+        fprintf(stderr, "[msd] launch nscen %d  work %p (+%zu B)  follow %p  queue %p  prof %p  scen %p  z %p  lam %p  stats %p  hist %p  %s  grid caps %d %d %d\n",
                 nscen, (void *)h->d_work, sizeof(double)*h->cap_work, (void *)h->d_follow, (void *)queue, (void *)h->d_prof, (const void *)d_scen, (void *)d_z, (void *)d_lam, (void *)d_stats, (void *)d_hist,
-                h->NT, h->SPT, h->NT2, h->SPT2, h->lds_bytes, h->lds_bytes2, h->max_grid, h->max_grid_lsq, h->max_grid2);
+                msd_host::plan_text(h->plan, h->plan.kernel_soc).c_str(), h->plan.max_grid, h->plan.max_grid_lsq, h->plan.max_grid2);
 #endif
-    return msd_host::launch_plan(plan_of(h), h->stream, h->d_work, h->d_follow, queue, nscen, d_scen, d_ovr, d_z, d_lam, d_stats, d_hist, hist_cap, ws, nullptr, e0, e1);
+    return msd_host::launch_plan(h->plan, h->stream, h->d_work, h->d_follow, queue, nscen, d_scen, d_ovr, d_z, d_lam, d_stats, d_hist, hist_cap, ws, nullptr, e0, e1);
 }
 
 int msd_solve_batch_device(msd_handle h, int nscen, const double *d_scen, double *d_z, double *d_lam, double *d_stats)
@@ -518,7 +573,7 @@ int msd_solve_batch_device_ex(msd_handle h, int nscen, const double *d_scen, con
 int msd_problem_geometry(msd_handle h, int *threads_per_scenario, int *nodes_per_thread)
 {
     if (!h || !threads_per_scenario || !nodes_per_thread) return fail(MSD_E_INVALID, "bad argument");
-    *threads_per_scenario = h->NT; *nodes_per_thread = h->SPT;
+    *threads_per_scenario = h->plan.NT; *nodes_per_thread = h->plan.SPT;
     return MSD_OK;
 }
 
@@ -596,7 +651,7 @@ static int check_batch(msd_handle h, int nscen, const double *scen, const double
                 !(o[MSD_OV_TOTAL_MASS] >= 0))
                 return fail(MSD_E_INVALID, "invalid rolling-stock override");
             /* the kernels with the row structure compiled in take both power rows as two-sided (finite by construction in the problem record: ocp.py:186-187) */
-            if (h->fused_family && (!std::isfinite(o[MSD_OV_PW_UPPER]) || !std::isfinite(o[MSD_OV_PW_LOWER])))
+            if (h->plan.fused_family && (!std::isfinite(o[MSD_OV_PW_UPPER]) || !std::isfinite(o[MSD_OV_PW_LOWER])))
                 return fail(MSD_E_INVALID, "rolling-stock override with an infinite power bound on a problem whose power rows are bounded");
         }
     for (int k = 0; k < nscen; k++) {
@@ -606,7 +661,7 @@ static int check_batch(msd_handle h, int nscen, const double *scen, const double
         if (!(s[MSD_SC_V0SQ] > 0) || !(s[MSD_SC_VNSQ] > 0)) return fail(MSD_E_INVALID, "velocities must be positive");
     }
     if (z_guess) {
-        const size_t nz = msd_problem_nz(h);
+        const size_t nz = h->plan.nz;
         for (size_t k = 0; k < nz*(size_t)nscen; k++)
             if (!std::isfinite(z_guess[k])) return fail(MSD_E_INVALID, "warm start guess must be finite");
     }
@@ -626,7 +681,7 @@ static double *device_address(const double *p)
 static int enqueue_downloads(msd_handle h, int nscen, double *z_out, double *lam_out, double *stats)
 {
     HIP_TRY(hipSetDevice(h->device));
-    const size_t nz = msd_problem_nz(h), nl = (size_t)msd_problem_rows_per_interval(h)*h->P.N;
+    const size_t nz = h->plan.nz, nl = h->plan.nl;
     if (!h->last_direct) {
         HIP_TRY(hipMemcpyAsync(z_out, h->d_z, sizeof(double)*nz*nscen, hipMemcpyDeviceToHost, h->stream));
         if (lam_out) HIP_TRY(hipMemcpyAsync(lam_out, h->d_lam, sizeof(double)*nl*nscen, hipMemcpyDeviceToHost, h->stream));
@@ -644,7 +699,7 @@ static int enqueue_batch(msd_handle h, int nscen, const double *scen, const doub
                          double *z_out, double *lam_out, double *stats, int shift = -1, bool defer_downloads = false)
 {
     HIP_TRY(hipSetDevice(h->device));
-    const size_t nz = msd_problem_nz(h), nl = (size_t)msd_problem_rows_per_interval(h)*h->P.N;
+    const size_t nz = h->plan.nz;
     if (nscen > h->cap_scen) {
         hipFree(h->d_scen); hipFree(h->d_ovr); hipFree(h->d_z); hipFree(h->d_lam); hipFree(h->d_stats); hipFree(h->d_z2); hipFree(h->d_stats2);
         h->d_scen = h->d_ovr = h->d_z = h->d_lam = h->d_stats = h->d_z2 = h->d_stats2 = nullptr; h->cap_scen = 0; h->prev_nscen = 0;
@@ -669,20 +724,20 @@ static int enqueue_batch(msd_handle h, int nscen, const double *scen, const doub
     ws.stride = (long long)nz;
     if (shift >= 0) {
         /* guesses = the previous solutions of this handle, `shift` intervals down the horizon: a tail of each stored z */
-        const int stp = 4 + h->P.withPn;
+        const int stp = 4 + h->plan.P.withPn;
         if (h->prev_nscen == 0 && h->last_direct)
             return fail(MSD_E_INVALID, "the previous solve of this handle stored its results in host memory directly (msd_problem_direct_results): the device holds no copy a shifted warm start could begin from");
         if (h->prev_nscen != nscen || h->prev_stp != stp || h->prev_nz - stp*shift != (int)nz)
             return fail(MSD_E_INVALID, "no previous solve of this handle matches the shifted warm start (same batch, horizon longer by `shift` intervals)");
         ws.d_guess = h->d_z + (size_t)stp*shift; ws.stride = h->prev_nz; ws.d_status = h->d_stats; ws.mu = mu_init; ws.push = bound_push;
         std::swap(h->d_z, h->d_z2); std::swap(h->d_stats, h->d_stats2);       /* results go to the other pair */
-        if (h->keep_duals && h->prev_dual_nodes == h->P.N + 1 + shift) {
+        if (h->keep_duals && h->prev_dual_nodes == h->plan.P.N + 1 + shift) {
             ws.d_dual_in = h->d_dual; ws.dual_stride = (long long)MSD_DUAL_STRIDE*h->prev_dual_nodes; ws.dual_shift = shift;
             std::swap(h->d_dual, h->d_dual2);
         }
     }
     if (h->keep_duals) {
-        const size_t need = (size_t)MSD_DUAL_STRIDE*(h->P.N + 1)*nscen;
+        const size_t need = (size_t)MSD_DUAL_STRIDE*(h->plan.P.N + 1)*nscen;
         if (need > h->cap_dual) {
             if (ws.d_dual_in) return fail(MSD_E_INVALID, "the multiplier buffers cannot grow between a solve and its shifted re-solve");
             hipFree(h->d_dual); hipFree(h->d_dual2); h->d_dual = h->d_dual2 = nullptr; h->cap_dual = 0; h->prev_dual_nodes = 0;
@@ -717,9 +772,8 @@ static int enqueue_batch(msd_handle h, int nscen, const double *scen, const doub
     if (rc != MSD_OK) return rc;
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     if (!d_hist && h->d_hist) { hipFree(h->d_hist); h->d_hist = nullptr; }      /* (enqueue_downloads copies a history only when this launch wrote one) */
-    h->prev_nscen = h->last_direct ? 0 : nscen; h->prev_nz = (int)nz; h->prev_stp = 4 + h->P.withPn;
-    h->prev_dual_nodes = h->keep_duals ? h->P.N + 1 : 0;
-    (void)nl;
+    h->prev_nscen = h->last_direct ? 0 : nscen; h->prev_nz = (int)nz; h->prev_stp = 4 + h->plan.P.withPn;
+    h->prev_dual_nodes = h->keep_duals ? h->plan.P.N + 1 : 0;
     if (!defer_downloads) return enqueue_downloads(h, nscen, z_out, lam_out, stats);
     return MSD_OK;
 }
@@ -780,15 +834,14 @@ int msd_solve_batch_multi(const msd_handle *handles, int nhandles, int nscen, co
     if (!handles || nhandles < 1 || nscen < 1) return fail(MSD_E_INVALID, "bad argument");
     for (int k = 0; k < nhandles; k++) {
         if (!handles[k]) return fail(MSD_E_INVALID, "null handle");
-        if (msd_problem_nz(handles[k]) != msd_problem_nz(handles[0]) || handles[k]->P.N != handles[0]->P.N ||
-            msd_problem_rows_per_interval(handles[k]) != msd_problem_rows_per_interval(handles[0]))
+        if (handles[k]->plan.nz != handles[0]->plan.nz || handles[k]->plan.P.N != handles[0]->plan.P.N || handles[k]->plan.nl != handles[0]->plan.nl)
             return fail(MSD_E_INVALID, "the handles of a multi-device solve must hold the same problem");
         for (int j = 0; j < k; j++)
             if (handles[j] == handles[k]) return fail(MSD_E_INVALID, "a handle appears twice");
     }
     int rc = check_batch(handles[0], nscen, scen, overrides, z_guess, mu_init, bound_push, z_out, stats);
     if (rc != MSD_OK) return rc;
-    const size_t nz = msd_problem_nz(handles[0]), nl = (size_t)msd_problem_rows_per_interval(handles[0])*handles[0]->P.N;
+    const size_t nz = handles[0]->plan.nz, nl = handles[0]->plan.nl;
     std::vector<int> lo(nhandles + 1);
     for (int k = 0; k <= nhandles; k++) lo[k] = (int)(((long long)nscen*k)/nhandles);
     int first_error = MSD_OK;
@@ -892,7 +945,7 @@ int msd_stage_eval(msd_handle h, int n, const double *b, const double *w, const 
     double *d_in = h->d_eval, *d_out = h->d_eval + 5*(size_t)n;
     const double *src[5] = {b, w, ds, grad, curv};
     for (int k = 0; k < 5; k++) hipMemcpyAsync(d_in + (size_t)k*n, src[k], sizeof(double)*n, hipMemcpyHostToDevice, h->stream);
-    hipLaunchKernelGGL(msd::stage_eval_kernel<0>, dim3((n + 255)/256), dim3(256), 0, h->stream, h->P, n, d_in, d_in + n, d_in + 2*(size_t)n, d_in + 3*(size_t)n,
+    hipLaunchKernelGGL(msd::stage_eval_kernel<0>, dim3((n + 255)/256), dim3(256), 0, h->stream, h->plan.P, n, d_in, d_in + n, d_in + 2*(size_t)n, d_in + 3*(size_t)n,
                        d_in + 4*(size_t)n, d_out);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out12, d_out, sizeof(double)*12*n, hipMemcpyDeviceToHost, h->stream);

@@ -5,11 +5,19 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 
 #include "msd_kernel.hpp"
 #include "msd_geometry.hpp"
 #include "../../include/mseetc_aux.h"
+
+namespace msd {
+/* (msd_kernels_stream4.hip; declared here and not in msd_geometry.hpp, which every kernel unit depends on) */
+Geometry pick_stream_geometry_general_dynamic(int N);
+Geometry pick_stream_geometry_general_intloss(int N);
+}
 
 namespace msd_host {
 
@@ -37,11 +45,44 @@ struct Plan {
     int max_grid = 0, max_grid_lsq = 0, max_grid2 = 0;      /* resident workgroups of the three */
     bool fused_family = false;                        /* `kernel` runs the fused iteration only (needs a profile start or a primal-dual warm start) */
     size_t work_doubles = 0;                          /* work area of one workgroup */
+    size_t work_area() const { return work_doubles*(size_t)std::max(max_grid, std::max(max_grid2, max_grid_lsq)); }      /* ... of as many as any of the kernels keeps resident */
     int nz = 0, nl = 0;                               /* variables / constraint multipliers per scenario */
 };
 
 int check_desc(const msd_problem_desc *d);
-int make_plan(int device, const msd_problem_desc *d, Plan *out);      /* (check_desc() must have accepted d) */
+int select_plan(const msd_problem_desc *d, Plan *out, msd::Geometry *geo);      /* the plan without what the device says (max_grid*, kernel_soc); check_desc() must have accepted d */
+int make_plan(int device, const msd_problem_desc *d, Plan *out);               /* select_plan + what `device` says */
+/* one line of text about a plan: NT SPT lds_bytes stream fused_family work_doubles nz nl NT2 SPT2 lds_bytes2 and the symbol names of kernel, kernel_lsq,
+ * kernel2 and `soc` ("-": none, "?": a pointer that is no exported symbol) -- msd_plan_describe and the MSD_DEBUG_PTRS print of the diagnostic builds */
+std::string plan_text(const Plan &pl, msd::KernelFn soc);
+
+/* the transcription a description asks for: which kernel family solves it */
+enum Family { STATIC, DYNAMIC, INTLOSS, INTLOSS_TABLE, GENERAL, GENERAL_DYNAMIC, GENERAL_INTLOSS };
+inline Family family_of(const msd_problem_desc *d)
+{
+    const bool dyn = d->loss_kind == 2, gen = d->integrator != 0, intloss = d->integrate_losses != 0 && d->energy_optimal != 0;
+    if (dyn && intloss) return INTLOSS_TABLE;      /* the loss table integrated over the running time (msd_lossint_table.hpp: DYN = LOSS_INTEGRATED_TABLE) */
+    if (gen) return dyn ? GENERAL_DYNAMIC : intloss ? GENERAL_INTLOSS : GENERAL;
+    return intloss ? INTLOSS : dyn ? DYNAMIC : STATIC;
+}
+/* the structure of the reference's rolling stock, where the description has it: msd::FULL_BOTH / FULL_RG / FULL_TIME_BOTH / FULL_TIME_RG, or 0 */
+inline int structure_of(const msd_problem_desc *d)
+{
+    /* power rows (finite by construction: ocp.py:186-187) and finite acceleration bounds (ocp.py:113-114) */
+    if (d->has_power_rows == 0 || !std::isfinite(d->acc_min) || !std::isfinite(d->acc_max) || !std::isfinite(d->pw_upper) || !std::isfinite(d->pw_lower)) return 0;
+    /* energy objective: both brakes, or the regenerative brake alone (forceMinPn = 0: the reference's scripts) */
+    if (d->energy_optimal != 0) return d->with_pn_brake != 0 ? msd::FULL_BOTH : msd::FULL_RG;
+    /* the time-optimal problem on the same rolling stock (energyOptimal = False: minimumTime, the twins of msd_mpc.hip): no loss rows */
+    return d->with_pn_brake != 0 ? msd::FULL_TIME_BOTH : msd::FULL_TIME_RG;
+}
+/* the kernels of a family for a horizon, LDS-resident and streamed (fn == nullptr: none): the one place that knows which picker takes which structure */
+msd::Geometry pick_resident(Family family, int N, int structure);
+msd::Geometry pick_streamed(Family family, int N, int structure);
+
+/* the profile of a description as the kernels read it: ds | grad | curv | bmax | pos in one buffer (pos: the running sum of ds) */
+constexpr size_t profile_doubles(int N) { return 5*(size_t)N + 2; }
+void pack_profile(const msd_problem_desc *d, double *out);
+inline void point_profile(msd::DevProb &P, const double *d_prof) { P.ds = d_prof; P.grad = P.ds + P.N; P.curv = P.grad + P.N; P.bmax = P.curv + P.N; P.pos = P.bmax + P.N + 1; }
 
 struct WarmStart { const double *d_guess = nullptr; long long stride = 0; const double *d_status = nullptr; double mu = 0, push = 0;
                    const double *d_dual_in = nullptr; long long dual_stride = 0; int dual_shift = 0; double *d_dual_out = nullptr;
@@ -64,34 +105,20 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
 }  // namespace msd_host
 
 struct msd_problem {
-    msd::DevProb P;
+    msd_host::Plan plan;                              /* of the problem the handle holds (profile pointers into d_prof); plan.kernel == nullptr: none -- its last (re)configuration failed */
     int device = 0;
-    int NT = 0;
-    size_t lds_bytes = 0;
-    int max_grid = 0;
-    msd::KernelFn kernel = nullptr;
-    msd::KernelFn kernel_lsq = nullptr;               /* first pass for launches that need the least-squares multiplier estimate (msd::Geometry::fn_lsq) */
-    int max_grid_lsq = 0;
-    msd::KernelFn kernel2 = nullptr;                  /* follow-up kernel of a split solve (msd::Geometry::fn2), its resident workgroups and the list between the two */
-    msd::KernelFn kernel_soc = nullptr;               /* first pass with the second-order correction inside the fused iteration (msd::Geometry::fn_soc; same launch as `kernel`) */
-    volatile int *h_soc_seen = nullptr;               /* mapped host word: a launch of the handle handed a second-order correction over (launch() then takes kernel_soc) */
+    volatile int *h_soc_seen = nullptr;               /* mapped host word: a launch of the handle handed a second-order correction over (launch() then takes plan.kernel_soc) */
     int *d_soc_seen = nullptr;                        /* its device address */
-    int max_grid2 = 0;
-    int NT2 = 0, SPT2 = 0; size_t lds_bytes2 = 0;     /* launch geometry of the follow-up kernel */
-    int *d_follow = nullptr; size_t cap_follow = 0;
-    bool fused_family = false;                        /* `kernel` runs the fused iteration only (needs a profile start or a primal-dual warm start) */
+    int *d_follow = nullptr; size_t cap_follow = 0;   /* the list between the two kernels of a split solve */
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double *d_prof = nullptr, *d_loss = nullptr;      /* ds | grad | curv | bmax | pos; loss table */
     double *h_stage = nullptr; size_t cap_stage = 0;  /* pinned staging buffer for the profile upload */
-    double *d_work = nullptr;                         /* private work areas of the resident workgroups (msd::work_doubles each) */
+    double *d_work = nullptr;                         /* private work areas of the resident workgroups (plan.work_doubles each) */
     double *d_eval = nullptr; size_t cap_eval = 0;    /* msd_stage_eval: inputs and outputs of n intervals (17 n doubles), grown on demand */
     int *d_queue = nullptr;                           /* scenario counters of the launches (a ring: launches in flight on the stream each own one) */
     int queue_slot = 0;
     size_t cap_work = 0;
-    int SPT = 0;
-    bool stream_kernel = false;                       /* the problem runs on a streamed kernel (stage blocks in device memory) */
-    size_t work_per_wg = 0;                           /* doubles of work area per workgroup */
     int cap_N = 0, cap_loss = 0, cap_nz = 0, cap_nl = 0;
     /* grow-only scratch of the host-buffer entry point */
     double *d_scen = nullptr, *d_ovr = nullptr, *d_z = nullptr, *d_lam = nullptr, *d_stats = nullptr, *d_hist = nullptr, *d_guess = nullptr;

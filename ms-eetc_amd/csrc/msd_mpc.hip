@@ -204,11 +204,9 @@ int msd_mpc_create(msd_handle h, msd_handle twin, const msd_mpc_plan *plan, msd_
             if (rc == MSD_OK) rc = msd_host::make_plan(h->device, t, &m->tw[k]);
         }
         if (rc != MSD_OK) break;
-        prof += 5*(size_t)d->num_intervals + 2;
-        const msd_host::Plan &p = m->pl[k];
-        work = std::max(work, p.work_doubles*(size_t)std::max(p.max_grid, std::max(p.max_grid2, p.max_grid_lsq)));
-        if (twin) { const msd_host::Plan &t = m->tw[k]; work = std::max(work, t.work_doubles*(size_t)std::max(t.max_grid, std::max(t.max_grid2, t.max_grid_lsq))); }
-        m->nz_max = std::max(m->nz_max, p.nz); m->nodes_max = std::max(m->nodes_max, d->num_intervals + 1);
+        prof += msd_host::profile_doubles(d->num_intervals);
+        work = std::max(work, std::max(m->pl[k].work_area(), twin ? m->tw[k].work_area() : (size_t)0));
+        m->nz_max = std::max(m->nz_max, m->pl[k].nz); m->nodes_max = std::max(m->nodes_max, d->num_intervals + 1);
         if (twin) m->nz_tw_max = std::max(m->nz_tw_max, m->tw[k].nz);
     }
     if (rc != MSD_OK) { msd_mpc_destroy(m); return rc; }
@@ -219,16 +217,10 @@ int msd_mpc_create(msd_handle h, msd_handle twin, const msd_mpc_plan *plan, msd_
     size_t off = 0;
     for (int k = 0; k < m->K; k++) {
         const msd_problem_desc *d = plan->problems + k;
-        const int N = d->num_intervals;
-        double *ds = stage.data() + off, *grad = ds + N, *curv = grad + N, *bmax = curv + N, *pos = bmax + N + 1;
-        std::copy(d->ds, d->ds + N, ds); std::copy(d->grad, d->grad + N, grad); std::copy(d->curv, d->curv + N, curv); std::copy(d->bmax, d->bmax + N + 1, bmax);
-        pos[0] = 0;
-        for (int i = 0; i < N; i++) pos[i + 1] = pos[i] + d->ds[i];
-        for (msd_host::Plan *p : {&m->pl[k], twin ? &m->tw[k] : (msd_host::Plan *)nullptr}) {
-            if (!p) continue;
-            p->P.ds = m->d_prof + off; p->P.grad = p->P.ds + N; p->P.curv = p->P.grad + N; p->P.bmax = p->P.curv + N; p->P.pos = p->P.bmax + N + 1;
-        }
-        off += 5*(size_t)N + 2;
+        msd_host::pack_profile(d, stage.data() + off);
+        msd_host::point_profile(m->pl[k].P, m->d_prof + off);
+        if (twin) msd_host::point_profile(m->tw[k].P, m->d_prof + off);
+        off += msd_host::profile_doubles(d->num_intervals);
     }
     if (hipMemcpy(m->d_prof, stage.data(), sizeof(double)*prof, hipMemcpyHostToDevice) != hipSuccess) { msd_mpc_destroy(m); return fail(MSD_E_HIP, "profile upload failed"); }
     {

@@ -125,6 +125,7 @@ def lib():
                                            _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, ctypes.c_double, ctypes.c_double, _dptr, _dptr]
 
         L.msd_tuning.argtypes = [ctypes.c_char_p, ctypes.c_int]
+        L.msd_plan_describe.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_char_p, ctypes.c_int]
         L.msd_fastmath_probe.argtypes = [ctypes.c_int, ctypes.c_int] + [_dptr]*4
         L.msd_host_alloc.argtypes = [ctypes.c_ulonglong, ctypes.POINTER(vp)]
         L.msd_host_free.argtypes = [vp]

@@ -119,3 +119,26 @@ def test_front_end_packs_the_same_problem_as_the_oracle_packer():
             assert getattr(d, a) == p.dp[DP[k]], a
         for arr, ref in zip(d._keep, (p.ds, p.grad, p.curv, p.bmax)):
             assert np.array_equal(arr, ref)
+
+
+def test_plan_selection_matches_the_recorded_table(built):
+    """
+    Which kernels, launch geometry, LDS and work sizes and which error every kind of description gets (msd_plan_describe over the enumeration of
+    tests/golden/make_plan_table.py: 288 descriptions, the horizons around every boundary of the pickers, the two tuning switches) against
+    tests/golden/plan_table.json, exactly.  A change of the selection shows here as the runs that moved.
+    """
+    import importlib.util
+    import json
+    from mseetc import _device
+    spec = importlib.util.spec_from_file_location('make_plan_table', ROOT / 'tests' / 'golden' / 'make_plan_table.py')
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = json.loads(gen.TABLE.read_text())
+    got = gen.enumerate_plans(_device.lib())
+    assert len(got['table']) == 288*3 and list(got['table']) == list(want['table'])
+    assert not [l for l in got['lines'] if '?' in l]      # every kernel pointer resolved to its symbol
+    for key, entry in got['table'].items():
+        runs = [[a, b, got['lines'][k]] for a, b, k in entry['runs']]
+        assert runs == [[a, b, want['lines'][k]] for a, b, k in want['table'][key]['runs']], key
+        assert entry['sha256'] == want['table'][key]['sha256'], key
+    assert got['lines'] == want['lines']

@@ -1529,3 +1529,68 @@ def test_follow_up_kernels_are_deterministic_launch_to_launch(case, tmp_path):
         if first['stats'][k, ST['N_RESTO']] == 0 and ref['stats']['N_RESTO'] == 0 and ref['stats']['ITERS'] <= 100:
             assert abs(int(first['iterations'][k]) - int(ref['stats']['ITERS'])) <= 2, (case, k, first['iterations'][k], ref['stats']['ITERS'])
         assert abs(first['cost'][k] - ref['stats']['OBJ']) <= 1e-6*max(1e-3, abs(ref['stats']['OBJ'])), (case, k)
+
+
+def _described(solver):
+    "the fields of msd_plan_describe's line for the solver's description"
+    import ctypes
+    from mseetc import _device
+    buf = ctypes.create_string_buffer(4096)
+    _device._check(_device.lib().msd_plan_describe(ctypes.byref(solver._desc), buf, len(buf)))
+    return dict(f.split('=', 1) for f in buf.value.decode().split())
+
+
+def test_handle_runs_the_described_plan():
+    """
+    A handle runs the plan msd_plan_describe reports for its description (tests/test_abi.py pins those lines against tests/golden/plan_table.json on
+    the CPU): geometry() against NT SPT of the line, and one solve, at the smallest shapes on each side of a code path of the plan's selection --
+    both brakes at N = 63 (64 x 1 first pass, the 64 x 2 follow-up kernel: from the reference's starting point, through the least-squares first
+    pass) and N = 64, the dynamic loss model at N = 100 (resident first pass, streamed follow-up), collocation at N = 40, the streamed kernel at
+    N = 700.  Then a reconfiguration the selection rejects: MSD_E_UNSUPPORTED, the handle holds no problem until a valid one, which solves.
+    """
+    from mseetc import _device
+    from mseetc.ocp import casadiSolver
+    from mseetc.train import Train
+    from mseetc.efficiency import totalLossesFunction
+    both = cases.train_fig10(); both.forceMinPn = cases.train_default().forceMinPn
+    dyn = Train(config={'id': 'NL_Intercity_VIRM6'}); dyn.forceMinPn = 0
+    dyn.powerLosses = totalLossesFunction(dyn, auxiliaries=27000, etaGear=0.96)      # (test_dynamic_loss_model_vs_oracle)
+    rk = dict(numSteps=1, numApproxSteps=1)
+    shapes = [('both_63', both, cases.track_00(30000), dict(numIntervals=63, maxIterations=800, integrationOptions=rk), 'reference', [1300.0, 16875.0], {}, (64, 1, 64, 2)),
+              ('both_64', both, cases.track_00(30000), dict(numIntervals=64, integrationOptions=rk), 'profile', [1300.0], {}, (64, 2, 64, 2)),
+              ('dynamic_100', dyn, cases.track_00(8500), dict(numIntervals=100, integrationOptions=rk), 'reference', [272.4726*1.2], dict(terminalVelocity=100/3.6, initialVelocity=1), None),
+              ('collocation_40', cases.train_default(), cases.track_00(20000), dict(numIntervals=40, integrationMethod='IRK', integrationOptions=dict(order=2, **rk)), 'profile', [760.0], {}, None),
+              ('streamed_700', cases.train_default(), cases.track_00(), dict(numIntervals=700, integrationOptions=rk), 'profile', [1541.0], {}, (512, 2, 512, 2))]
+    for name, train, track, opts, start, T, kw, want in shapes:
+        s = casadiSolver(train, track, dict(dict(maxIterations=500), **opts), startingPoint=start)
+        line = _described(s)
+        print(name, line)
+        assert '?' not in line.values()
+        assert s.problem.geometry() == (int(line['NT']), int(line['SPT'])), name
+        assert want is None or tuple(int(line[k]) for k in ('NT', 'SPT', 'NT2', 'SPT2')) == want, name
+        assert (line['stream'] == '1') == (name == 'streamed_700') and (not name.startswith('both') or line['kernel_lsq'] != '-')
+        before = s.problem.follow_counts()[0]
+        res = s.solveBatch(T, **kw)
+        print(name, res['status'], res['iterations'], s.problem.follow_counts())
+        assert np.all(res['status'] == 0), (name, res['status'])
+        if name == 'both_63':
+            assert s.problem.follow_counts()[0] - before >= 1      # the loose schedule went through the 64 x 2 follow-up kernel
+        if name == 'dynamic_100':
+            # a description the selection rejects (the dynamic loss model ends at 1023 intervals): the handle holds no problem until the next valid one
+            long = casadiSolver(train, track, dict(numIntervals=1100, maxIterations=500, integrationOptions=rk), startingPoint=start)
+            with pytest.raises(_device.DeviceError, match='msd error -3: numIntervals = 1100 exceeds the 1023 intervals'):
+                s.problem.reconfigure(long._desc)
+            with pytest.raises(ValueError, match=r'the handle holds no problem: its last \(re\)configuration failed'):
+                s.solveBatch(T, **kw)
+            # ... and the same after a description the argument checks reject
+            s.problem.reconfigure(s._desc)
+            s._desc.max_iterations = 0
+            with pytest.raises(ValueError, match='Maximum number of iterations'):
+                s.problem.reconfigure(s._desc)
+            s._desc.max_iterations = 500
+            with pytest.raises(ValueError, match=r'the handle holds no problem: its last \(re\)configuration failed'):
+                s.solveBatch(T, **kw)
+            s.problem.reconfigure(s._desc)
+            again = s.solveBatch(T, **kw)
+            assert np.array_equal(again['status'], res['status']) and np.array_equal(again['z'], res['z'])
+        s.close()
