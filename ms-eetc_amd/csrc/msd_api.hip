@@ -26,12 +26,28 @@ namespace {
 thread_local std::string g_err;
 }
 
+/* the lookups of the kernel units (msd_kernels_<unit>.hip: kernels_<unit>) */
+#define MSD_KERNEL_UNITS(X) X(full) X(full2) X(full3) X(full4) X(rg) X(rg2) X(static) X(time) X(time2) X(dynamic) X(dynamic2) X(dynamic3) X(stream) X(stream2) X(stream3) \
+    X(stream4) X(stream5) X(stream6) X(stream7) X(compose) X(general) X(general2) X(intloss) X(intloss_table) X(intloss_table2)
 namespace msd {
-Tuning &tuning() { static Tuning t; return t; }
+#define X(unit) KernelFn kernels_##unit(const KernelId &id);
+MSD_KERNEL_UNITS(X)
+#undef X
 }
 
 namespace msd_host {
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
+Tuning &tuning() { static Tuning t; return t; }
+
+msd::KernelFn find_kernel(const msd::KernelId &id)
+{
+    if (!id) return nullptr;
+#define X(unit) if (const msd::KernelFn fn = msd::kernels_##unit(id)) return fn;
+    MSD_KERNEL_UNITS(X)
+#undef X
+    return nullptr;
+}
+bool has_kernel(const msd::KernelId &id) { return find_kernel(id) != nullptr; }
 }
 using msd_host::fail;
 
@@ -112,104 +128,42 @@ static int kernel_limits(int device, const void *fn, int threads, size_t lds, in
 }
 
 
-/* the LDS-resident kernels of a family.  The pickers take the structure their family has kernels for: general / intloss the one with both brakes (a
- * bool), dynamic the two of the energy problem, static every one */
-msd::Geometry pick_resident(Family family, int N, int structure)
-{
-    const bool full = structure == msd::FULL_BOTH;
-    switch (family) {
-    case INTLOSS_TABLE: return msd::pick_geometry_intloss_table(N);
-    case GENERAL_DYNAMIC: return msd::pick_geometry_general_dynamic(N);
-    case GENERAL_INTLOSS: return msd::pick_geometry_general_intloss(N);
-    case GENERAL: return msd::pick_geometry_general(N, full);
-    case INTLOSS: return msd::pick_geometry_intloss(N, full);
-    case DYNAMIC: return msd::pick_geometry_dynamic(N, (full || structure == msd::FULL_RG) ? structure : 0);
-    case STATIC: return msd::pick_geometry_static(N, structure);
-    }
-    return {0, 0, nullptr};
-}
-
-/* the streamed kernels of a family (stage blocks in device memory): first pass + follow-up kernel.  Only the static family has first passes with a
- * structure compiled in, the two of the energy problem */
-msd::Geometry pick_streamed(Family family, int N, int structure)
-{
-    switch (family) {
-    case INTLOSS_TABLE: return msd::pick_stream_geometry_intloss_table(N);
-    case GENERAL_DYNAMIC: return msd::pick_stream_geometry_general_dynamic(N);
-    case GENERAL_INTLOSS: return msd::pick_stream_geometry_general_intloss(N);
-    case GENERAL: return msd::pick_stream_geometry_general(N);
-    case INTLOSS: return msd::pick_stream_geometry_intloss(N);
-    case DYNAMIC: return msd::pick_stream_geometry_dynamic(N);
-    case STATIC: return msd::pick_stream_geometry_static(N, (structure == msd::FULL_BOTH || structure == msd::FULL_RG) ? structure : 0);
-    }
-    return {0, 0, nullptr};
-}
-
-/* kernel geometry of a problem's horizon and structure, problem record without the profile pointers: everything of a plan that needs no device
- * (geo_out: the geometry picked, with the follow-up kernel the plan takes) */
-int select_plan(const msd_problem_desc *d, Plan *out, msd::Geometry *geo_out)
+/* kernel geometry of a problem's horizon and structure, problem record without the profile pointers: everything of a plan that needs no
+ * device (soc_out: the first pass with the second-order correction inside that the geometry offers, or nullptr; make_plan decides) */
+int select_plan(const msd_problem_desc *d, Plan *out, msd::KernelFn *soc_out)
 {
     Plan &pl = *out;
     const int N = d->num_intervals;
     const Family family = family_of(d);
     const int structure = structure_of(d);
-    const bool gen = d->integrator != 0;
-    const bool wide = d->loss_kind == 2 || (d->integrate_losses != 0 && d->energy_optimal != 0);      /* stage blocks with the slack-b and slack-Fpb couplings */
-    msd::Geometry geo = pick_resident(family, N, structure);
-    size_t lds = geo.fn ? sizeof(double)*(size_t)(msd::lds_doubles(N, geo.NT*geo.SPT, wide, geo.xch, geo.red) + msd::coop_doubles(geo.NT, gen) + geo.extra) : 0;
-    if (!geo.fn || lds > 160*1024) {
+    const bool wide = msd_host::dyn_of(family) != msd::LOSS_STATIC;      /* stage blocks with the slack-b and slack-Fpb couplings */
+    msd::Geometry geo = resident(family, N, structure, tuning());
+    if (!geo.first || lds_bytes(geo, geo.first, N) > 160*1024) {
         /* the stage blocks do not fit the LDS of a compute unit: the streamed kernels keep them in device memory */
-        geo = pick_streamed(family, N, structure);
-        lds = sizeof(double)*(size_t)msd::lds_doubles_stream();
-        if (!geo.fn)
+        geo = streamed(family, N, structure, tuning());
+        if (!geo.first)
             return fail(MSD_E_UNSUPPORTED, family != STATIC ? "numIntervals = " + std::to_string(N) + " exceeds the 1023 intervals of the streamed kernels for the dynamic loss model, the collocation / adaptive shooting integrators and integrateLosses"
                                            : "numIntervals = " + std::to_string(N) + " exceeds the 5119 intervals of the streamed kernel");
     }
-    pl.NT = geo.NT; pl.SPT = geo.SPT; pl.lds_bytes = lds; pl.stream = geo.stream;
-    msd::DevProb &P = pl.P;
-    P.N = N; P.withPn = d->with_pn_brake != 0; P.hasPower = d->has_power_rows != 0; P.energyOpt = d->energy_optimal != 0;
-    P.numSteps = d->num_steps; P.numApprox = d->num_approx_steps; P.lossKind = d->loss_kind; P.maxIter = d->max_iterations;
-    P.sr0 = d->sr0; P.sr1 = d->sr1; P.sr2 = d->sr2; P.g = d->g; P.rho = d->rho; P.fmax = d->f_max; P.fmin = d->f_min; P.fminPn = d->f_min_pn;
-    P.pwU = d->pw_upper; P.pwL = d->pw_lower; P.accMin = d->acc_min; P.accMax = d->acc_max; P.ct = d->loss_ct; P.cr = d->loss_cr;
-    P.vminSq = d->vmin_sq; P.objDen = d->obj_den; P.tol = d->tol;
-    P.guess = nullptr; P.guessStride = 0; P.guessStatus = nullptr; P.warmMu = 0; P.warmPush = 0; P.start = d->start_kind; P.lossMass = 0; P.queue = nullptr; P.follow = nullptr; P.list = nullptr; P.socSeen = nullptr; P.dualOut = nullptr; P.dualIn = nullptr; P.dualInStride = 0; P.dualShift = 0;
-    P.ds = P.grad = P.curv = P.bmax = P.pos = nullptr;      /* (the owner of the profile buffer fills these) */
-    P.loss = nullptr; P.lossCoef = nullptr;
-    P.integ = d->integrator; P.collD = d->coll_degree; P.newtonIters = d->newton_iterations; P.intAtol = d->int_abstol; P.intRtol = d->int_reltol;
-    P.coll = nullptr;
-    P.resto = d->no_restoration ? 0 : 1;
-    P.oneAttempt = 0;
-    P.wdTrigger = d->watchdog_trigger == 0 ? 10 : d->watchdog_trigger;      /* IPOPT's default */
-    if (d->integrator == MSD_INTEGRATOR_ADAPTIVE) P.numApprox = 0;      /* train.py:314 */
-
-    pl.NT2 = geo.NT; pl.SPT2 = geo.SPT; pl.lds_bytes2 = lds;
-    if (geo.fn2 && geo.NT == 64 && geo.SPT == 1 && geo.xch == msd::XCH_FAST && structure == msd::FULL_BOTH) {
-        /* horizons of up to 63 intervals, both brakes: the first pass runs one node per lane, the follow-up kernel is the two-nodes-per-lane one (its second
-         * node slots stay idle; the follow-up kernel restarts a scenario from its starting point, so nothing ties its geometry to the first pass's -- and the
-         * family has no 64 x 1 follow-up instantiation).  The one-brake family has its 64 x 1 follow-up kernel back (round 6: msd_kernels_rg2.hip) */
-        geo.fn2 = msd::follow_kernel_full(64, 2);
-        pl.NT2 = 64; pl.SPT2 = 2;
-        pl.lds_bytes2 = sizeof(double)*(size_t)msd::lds_doubles(N, 128, wide, geo.xch, geo.red);
-    }
     size_t work2 = 0;
-    if (!geo.fn2 && !geo.stream) {
-        /* an LDS-resident kernel without a follow-up kernel of its own geometry (every family but the two with the structure of the reference's rolling
-         * stock compiled in): a first-pass kernel -- the general iteration without the restoration phase and the watchdog procedure; a scenario that needs
-         * either is followed up by the streamed kernel of the family (msd_kernel.hpp: FAMILY_HAS_RESTO, WD_HANDOVER).  The follow-up restarts the
-         * scenario, so the two geometries need not agree; and the structure does not matter here: it selects the streamed first pass only, the
-         * streamed follow-up kernel is the general one whatever the structure */
-        const msd::Geometry g2 = pick_streamed(family, N, structure);
-        if (!g2.fn2) return fail(MSD_E_UNSUPPORTED, "no follow-up kernel for numIntervals = " + std::to_string(N));
-        geo.fn2 = g2.fn2; pl.NT2 = g2.NT; pl.SPT2 = g2.SPT;
-        pl.lds_bytes2 = sizeof(double)*(size_t)msd::lds_doubles_stream();
-        work2 = msd::stream_doubles(N, g2.NT*g2.SPT, wide);
+    if (!geo.follow) {
+        /* an LDS-resident kernel without a follow-up kernel of its own (every family but the fused one): a first-pass kernel -- the general iteration
+         * without the restoration phase and the watchdog procedure; a scenario that needs either is followed up by the streamed kernel of the family
+         * (msd_kernel.hpp: FAMILY_HAS_RESTO, WD_HANDOVER).  The follow-up restarts the scenario, so the two geometries need not agree; and the structure
+         * does not matter here: it selects the streamed first pass only, the streamed follow-up kernel is the general one whatever the structure */
+        geo.follow = streamed(family, N, structure, tuning()).follow;
+        if (!geo.follow) return fail(MSD_E_UNSUPPORTED, "no follow-up kernel for numIntervals = " + std::to_string(N));
+        work2 = msd::stream_doubles(N, geo.follow.NT*geo.follow.SPT, wide);
     }
-    pl.fused_family = geo.fn2 != nullptr && geo.xch == msd::XCH_FAST;
-    pl.work_doubles = geo.stream ? msd::stream_doubles(N, geo.NT*geo.SPT, wide) : std::max(work2, msd::work_doubles(std::max(geo.NT*geo.SPT, work2 ? 0 : pl.NT2*pl.SPT2)));
-    pl.nz = (4 + P.withPn)*N + 2; pl.nl = ((P.hasPower ? 2 : 0) + 3 + (P.energyOpt ? 2 : 0))*N;
-    pl.kernel = geo.fn; pl.kernel2 = geo.fn2; pl.kernel_lsq = geo.fn_lsq;
+    pl.NT = geo.first.NT; pl.SPT = geo.first.SPT; pl.lds_bytes = lds_bytes(geo, geo.first, N); pl.stream = geo.stream;
+    pl.NT2 = geo.follow.NT; pl.SPT2 = geo.follow.SPT; pl.lds_bytes2 = lds_bytes(geo, geo.follow, N);
+    fill_problem(pl.P, d);      /* (the owner of the profile buffer fills its pointers) */
+    pl.fused_family = geo.xch == msd::XCH_FAST;
+    pl.work_doubles = geo.stream ? msd::stream_doubles(N, pl.NT*pl.SPT, wide) : std::max(work2, msd::work_doubles(std::max(pl.NT*pl.SPT, work2 ? 0 : pl.NT2*pl.SPT2)));
+    pl.nz = (4 + pl.P.withPn)*N + 2; pl.nl = ((pl.P.hasPower ? 2 : 0) + 3 + (pl.P.energyOpt ? 2 : 0))*N;
+    pl.kernel = find_kernel(geo.first); pl.kernel2 = find_kernel(geo.follow); pl.kernel_lsq = find_kernel(geo.lsq);      /* (the ladder hands out only ids the build holds) */
     pl.kernel_soc = nullptr;
-    *geo_out = geo;
+    *soc_out = find_kernel(geo.soc);
     return MSD_OK;
 }
 
@@ -217,8 +171,8 @@ int select_plan(const msd_problem_desc *d, Plan *out, msd::Geometry *geo_out)
 int make_plan(int device, const msd_problem_desc *d, Plan *out)
 {
     Plan &pl = *out;
-    msd::Geometry geo{0, 0, nullptr};
-    int rc = select_plan(d, &pl, &geo);
+    msd::KernelFn soc = nullptr;
+    int rc = select_plan(d, &pl, &soc);
     if (rc != MSD_OK) return rc;
     int per_cu = 0, cus = 0;
     rc = kernel_limits(device, (const void *)pl.kernel, pl.NT, pl.lds_bytes, &per_cu);
@@ -238,10 +192,10 @@ int make_plan(int device, const msd_problem_desc *d, Plan *out)
         if (rc != MSD_OK) return rc;
         pl.max_grid_lsq = per_cu*cus;
     }
-    if (geo.fn_soc) {
+    if (soc) {
         /* (same launch as `kernel`; taken only when it is as resident) */
         int per_cu_soc = 0;
-        if (kernel_limits(device, (const void *)geo.fn_soc, pl.NT, pl.lds_bytes, &per_cu_soc) == MSD_OK && per_cu_soc*cus >= pl.max_grid) pl.kernel_soc = geo.fn_soc;
+        if (kernel_limits(device, (const void *)soc, pl.NT, pl.lds_bytes, &per_cu_soc) == MSD_OK && per_cu_soc*cus >= pl.max_grid) pl.kernel_soc = soc;
     }
     return MSD_OK;
 }
@@ -302,7 +256,7 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
         return MSD_OK;
     }
     P.list = d_list;      /* (not null: the first pass solves the scenarios of this list only -- the re-solves of msd_mpc.hip -- and hands over through `follow` as usual) */
-    /* split solves (msd::Geometry::fn2): first pass + follow-up kernel behind it on the stream, the list of unfinished scenarios between them.
+    /* split solves (msd::Geometry::follow): first pass + follow-up kernel behind it on the stream, the list of unfinished scenarios between them.
      * The first pass is the kernel without the least-squares multiplier estimate when every scenario can start without it (profile start,
      * primal-dual warm start), the one with it otherwise (the reference's starting point, a primal-only warm start) */
     const msd::KernelFn fn = (split && !first_pass) ? pl.kernel2 : plain ? ((ws.use_soc && pl.kernel_soc) ? pl.kernel_soc : pl.kernel) : pl.kernel_lsq;
@@ -351,8 +305,8 @@ const char *msd_last_error(void) { return g_err.c_str(); }
 int msd_tuning(const char *name, int value)
 {
     if (!name) return fail(MSD_E_INVALID, "null argument");
-    if (!strcmp(name, "no_full")) msd::tuning().no_full = value != 0;
-    else if (!strcmp(name, "two_nodes_per_lane")) msd::tuning().two_nodes_per_lane = value != 0;
+    if (!strcmp(name, "no_full")) msd_host::tuning().no_full = value != 0;
+    else if (!strcmp(name, "two_nodes_per_lane")) msd_host::tuning().two_nodes_per_lane = value != 0;
     else return fail(MSD_E_INVALID, std::string("unknown tuning switch: ") + name);
     return MSD_OK;
 }
@@ -363,12 +317,12 @@ int msd_plan_describe(const msd_problem_desc *d, char *buf, int len)
     int rc = check_desc(d);
     if (rc != MSD_OK) return rc;
     msd_host::Plan pl;
-    msd::Geometry geo{0, 0, nullptr};
-    rc = msd_host::select_plan(d, &pl, &geo);
+    msd::KernelFn soc = nullptr;
+    rc = msd_host::select_plan(d, &pl, &soc);
     if (rc != MSD_OK) return rc;
     static const char *const family[] = {"STATIC", "DYNAMIC", "INTLOSS", "INTLOSS_TABLE", "GENERAL", "GENERAL_DYNAMIC", "GENERAL_INTLOSS"};
     static const char *const structure[] = {"0", "FULL_BOTH", "FULL_RG", "FULL_TIME_BOTH", "FULL_TIME_RG"};
-    const std::string line = std::string("family=") + family[msd_host::family_of(d)] + " structure=" + structure[msd_host::structure_of(d)] + " " + msd_host::plan_text(pl, geo.fn_soc);
+    const std::string line = std::string("family=") + family[msd_host::family_of(d)] + " structure=" + structure[msd_host::structure_of(d)] + " " + msd_host::plan_text(pl, soc);
     if ((int)line.size() >= len) return fail(MSD_E_INVALID, "msd_plan_describe: the line needs " + std::to_string(line.size() + 1) + " bytes");
     memcpy(buf, line.c_str(), line.size() + 1);
     return MSD_OK;

@@ -11,13 +11,8 @@
 
 #include "msd_kernel.hpp"
 #include "msd_geometry.hpp"
+#include "msd_select.hpp"
 #include "../../include/mseetc_aux.h"
-
-namespace msd {
-/* (msd_kernels_stream4.hip; declared here and not in msd_geometry.hpp, which every kernel unit depends on) */
-Geometry pick_stream_geometry_general_dynamic(int N);
-Geometry pick_stream_geometry_general_intloss(int N);
-}
 
 namespace msd_host {
 
@@ -37,9 +32,9 @@ struct Plan {
     size_t lds_bytes = 0;
     bool stream = false;                              /* stage blocks in device memory (long horizons) */
     msd::KernelFn kernel = nullptr;                   /* complete kernel, or the first pass of a split solve (kernel2 != nullptr) */
-    msd::KernelFn kernel_lsq = nullptr;               /* first pass for launches that need the least-squares multiplier estimate (msd::Geometry::fn_lsq) */
-    msd::KernelFn kernel2 = nullptr;                  /* follow-up kernel of a split solve (msd::Geometry::fn2) */
-    msd::KernelFn kernel_soc = nullptr;               /* `kernel` with the second-order correction inside the fused iteration (msd::Geometry::fn_soc): WarmStart::use_soc */
+    msd::KernelFn kernel_lsq = nullptr;               /* first pass for launches that need the least-squares multiplier estimate (msd::Geometry::lsq) */
+    msd::KernelFn kernel2 = nullptr;                  /* follow-up kernel of a split solve (msd::Geometry::follow) */
+    msd::KernelFn kernel_soc = nullptr;               /* `kernel` with the second-order correction inside the fused iteration (msd::Geometry::soc): WarmStart::use_soc */
     int NT2 = 0, SPT2 = 0;                            /* its own launch geometry (it restarts a scenario from its starting point, so it need not share the first pass's) */
     size_t lds_bytes2 = 0;
     int max_grid = 0, max_grid_lsq = 0, max_grid2 = 0;      /* resident workgroups of the three */
@@ -50,34 +45,14 @@ struct Plan {
 };
 
 int check_desc(const msd_problem_desc *d);
-int select_plan(const msd_problem_desc *d, Plan *out, msd::Geometry *geo);      /* the plan without what the device says (max_grid*, kernel_soc); check_desc() must have accepted d */
+int select_plan(const msd_problem_desc *d, Plan *out, msd::KernelFn *soc);      /* the plan without what the device says (max_grid*, kernel_soc; soc: the candidate for it); check_desc() must have accepted d */
 int make_plan(int device, const msd_problem_desc *d, Plan *out);               /* select_plan + what `device` says */
 /* one line of text about a plan: NT SPT lds_bytes stream fused_family work_doubles nz nl NT2 SPT2 lds_bytes2 and the symbol names of kernel, kernel_lsq,
  * kernel2 and `soc` ("-": none, "?": a pointer that is no exported symbol) -- msd_plan_describe and the MSD_DEBUG_PTRS print of the diagnostic builds */
 std::string plan_text(const Plan &pl, msd::KernelFn soc);
 
-/* the transcription a description asks for: which kernel family solves it */
-enum Family { STATIC, DYNAMIC, INTLOSS, INTLOSS_TABLE, GENERAL, GENERAL_DYNAMIC, GENERAL_INTLOSS };
-inline Family family_of(const msd_problem_desc *d)
-{
-    const bool dyn = d->loss_kind == 2, gen = d->integrator != 0, intloss = d->integrate_losses != 0 && d->energy_optimal != 0;
-    if (dyn && intloss) return INTLOSS_TABLE;      /* the loss table integrated over the running time (msd_lossint_table.hpp: DYN = LOSS_INTEGRATED_TABLE) */
-    if (gen) return dyn ? GENERAL_DYNAMIC : intloss ? GENERAL_INTLOSS : GENERAL;
-    return intloss ? INTLOSS : dyn ? DYNAMIC : STATIC;
-}
-/* the structure of the reference's rolling stock, where the description has it: msd::FULL_BOTH / FULL_RG / FULL_TIME_BOTH / FULL_TIME_RG, or 0 */
-inline int structure_of(const msd_problem_desc *d)
-{
-    /* power rows (finite by construction: ocp.py:186-187) and finite acceleration bounds (ocp.py:113-114) */
-    if (d->has_power_rows == 0 || !std::isfinite(d->acc_min) || !std::isfinite(d->acc_max) || !std::isfinite(d->pw_upper) || !std::isfinite(d->pw_lower)) return 0;
-    /* energy objective: both brakes, or the regenerative brake alone (forceMinPn = 0: the reference's scripts) */
-    if (d->energy_optimal != 0) return d->with_pn_brake != 0 ? msd::FULL_BOTH : msd::FULL_RG;
-    /* the time-optimal problem on the same rolling stock (energyOptimal = False: minimumTime, the twins of msd_mpc.hip): no loss rows */
-    return d->with_pn_brake != 0 ? msd::FULL_TIME_BOTH : msd::FULL_TIME_RG;
-}
-/* the kernels of a family for a horizon, LDS-resident and streamed (fn == nullptr: none): the one place that knows which picker takes which structure */
-msd::Geometry pick_resident(Family family, int N, int structure);
-msd::Geometry pick_streamed(Family family, int N, int structure);
+Tuning &tuning();                                         /* the switches of msd_tuning() (msd_api.hip) */
+msd::KernelFn find_kernel(const msd::KernelId &id);      /* the instantiation in the kernel units (msd_kernels_*.hip); nullptr: none, also for the empty id */
 
 /* the profile of a description as the kernels read it: ds | grad | curv | bmax | pos in one buffer (pos: the running sum of ds) */
 constexpr size_t profile_doubles(int N) { return 5*(size_t)N + 2; }

@@ -1,21 +1,22 @@
-/* solve-kernel instantiations for the dynamic loss model(s); see msd_geometry.hpp */
+/* solve-kernel instantiations for the dynamic loss model: the first-pass kernels without a structure compiled in (with one: msd_kernels_dynamic2.hip,
+ * msd_kernels_dynamic3.hip); see msd_geometry.hpp, msd_select.hpp */
 #include <hip/hip_runtime.h>
-
-#include <cstdlib>
-#include <cstring>
 
 #include "msd_geometry.hpp"
 
 namespace msd {
-/* full: FULL_BOTH / FULL_RG -- the structure of the reference's rolling stock compiled in (every row on, power rows two-sided, energy objective; with /
- * without the pneumatic brake), where that instantiation exists (msd_kernels_dynamic2.hip, msd_kernels_dynamic3.hip); round 6: 438 k -> 508 k solves/s on
- * the figure-5 batch at N = 100.  The streamed kernel of the family follows up either way */
-Geometry pick_geometry_dynamic(int N, int full)
+KernelFn kernels_dynamic(const KernelId &id)
 {
-    if (full && !tuning().no_full) {
-        const Geometry g = full == FULL_BOTH ? pick_geometry_dynamic_full_both(N) : pick_geometry_dynamic_full_rg(N);
-        if (g.fn) return g;
-    }
-    return pick_geometry_t<LOSS_TABLE>(N);
+    MSD_KERNEL(64, 1, 1, LOSS_TABLE, false, false, 0, 1)
+    MSD_KERNEL(128, 1, 1, LOSS_TABLE, false, false, 0, 1)
+    MSD_KERNEL(64, 2, 1, LOSS_TABLE, false, false, 0, 1)
+    MSD_KERNEL(128, 2, 1, LOSS_TABLE, false, false, 0, 1)
+#ifndef MSD_MINIMAL_GEOMETRIES      /* tuning builds (tools/build_variant.py) */
+    MSD_KERNEL(192, 2, 1, LOSS_TABLE, false, false, 0, 1)
+    MSD_KERNEL(256, 2, 1, LOSS_TABLE, false, false, 0, 1)
+    MSD_KERNEL_UNUSED(192, 3, 1, LOSS_TABLE, false, false, 0, 1)
+    MSD_KERNEL(320, 2, 2, LOSS_TABLE, false, false, 0, 1)
+#endif
+    return nullptr;
 }
 }

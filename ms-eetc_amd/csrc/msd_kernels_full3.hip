@@ -5,14 +5,13 @@
 #include "msd_geometry.hpp"
 
 namespace msd {
-KernelFn follow_kernel_full(int NT, int SPT)
+KernelFn kernels_full3(const KernelId &id)
 {
-    /* (horizons of up to 63 intervals: the two-nodes-per-lane kernel follows up the one-node-per-lane first pass, msd_api.hip: make_plan launches it as 64 x 2) */
-    if (NT == 64 && SPT == 1) return solve_kernel<64, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2>;
-    if (NT == 64 && SPT == 2) return solve_kernel<64, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2>;
-    if (NT == 128 && SPT == 2) return solve_kernel<128, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2>;
-    if (NT == 192 && SPT == 2) return solve_kernel<192, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2>;
-    if (NT == 256 && SPT == 2) return solve_kernel<256, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2>;
+    /* (no 64 x 1 instantiation: the 64 x 2 kernel follows up the one-node-per-lane first pass, msd_select.hpp) */
+    MSD_KERNEL(64, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2)
+    MSD_KERNEL(128, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2)
+    MSD_KERNEL(192, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2)
+    MSD_KERNEL(256, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 2)
     return nullptr;
 }
 }

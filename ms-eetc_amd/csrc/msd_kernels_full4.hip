@@ -6,10 +6,10 @@
 #include "msd_geometry.hpp"
 
 namespace msd {
-KernelFn soc_kernel_full(int NT, int SPT, bool slds)
+KernelFn kernels_full4(const KernelId &id)
 {
-    if (NT == 64 && SPT == 1 && !slds) return solve_kernel<64, 1, 1, LOSS_STATIC, false, false, FULL_BOTH, 1, false, true>;
-    if (NT == 64 && SPT == 2 && slds) return solve_kernel<64, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 1, true, true>;
+    MSD_KERNEL(64, 1, 1, LOSS_STATIC, false, false, FULL_BOTH, 1, false, true)
+    MSD_KERNEL(64, 2, 1, LOSS_STATIC, false, false, FULL_BOTH, 1, true, true)
     return nullptr;
 }
-}  // namespace msd
+}

@@ -7,11 +7,10 @@
 #include "msd_geometry.hpp"
 
 namespace msd {
-Geometry pick_geometry_intloss_table(int N)
+KernelFn kernels_intloss_table(const KernelId &id)
 {
-    const int nodes = N + 1;
-    if (nodes <= 64) return {64, 1, solve_kernel<64, 1, 1, LOSS_INTEGRATED_TABLE, false, false, 0, 1>};
-    if (nodes <= 128) return {128, 1, solve_kernel<128, 1, 1, LOSS_INTEGRATED_TABLE, false, false, 0, 1>};
-    return {0, 0, nullptr};
+    MSD_KERNEL(64, 1, 1, LOSS_INTEGRATED_TABLE, false, false, 0, 1)
+    MSD_KERNEL(128, 1, 1, LOSS_INTEGRATED_TABLE, false, false, 0, 1)
+    return nullptr;
 }
 }

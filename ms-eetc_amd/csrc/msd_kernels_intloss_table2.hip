@@ -5,5 +5,10 @@
 #include "msd_geometry.hpp"
 
 namespace msd {
-Geometry pick_stream_geometry_intloss_table(int N) { return N + 1 <= 1024 ? stream_geometry_t<LOSS_INTEGRATED_TABLE, false, 2>() : Geometry{0, 0, nullptr}; }
+KernelFn kernels_intloss_table2(const KernelId &id)
+{
+    MSD_KERNEL(512, 2, 2, LOSS_INTEGRATED_TABLE, true, false, 0, 1)
+    MSD_KERNEL(512, 2, 2, LOSS_INTEGRATED_TABLE, true, false, 0, 2)
+    return nullptr;
+}
 }

@@ -4,28 +4,25 @@
  * msd_kernels_rg2.hip the follow-up kernels (general iteration, restoration phase, second attempt). */
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <cstring>
-
 #include "msd_geometry.hpp"
 
 namespace msd {
-/* the pickers below hand out XCH_FAST exchange arrays (and no reduction scratch for a single wave): the layout of a kernel whose Solver::FAST holds */
-static_assert(Solver<64, 2, LOSS_STATIC, false, false, FULL_RG, 1>::FAST && Solver<256, 2, LOSS_STATIC, false, false, FULL_RG, 3>::FAST, "the tuning switches of this build (MSD_PARALLEL_RICCATI) leave no fused iteration: pick_geometry_full would size the LDS wrongly");
-Geometry pick_geometry_full_rg(int N)
+/* the ladder hands these kernels XCH_FAST exchange arrays (and no reduction scratch for a single wave): the layout of a kernel whose Solver::FAST holds */
+static_assert(Solver<64, 2, LOSS_STATIC, false, false, FULL_RG, 1>::FAST && Solver<256, 2, LOSS_STATIC, false, false, FULL_RG, 3>::FAST, "the tuning switches of this build (MSD_PARALLEL_RICCATI) leave no fused iteration: the ladder of msd_select.hpp would size the LDS wrongly");
+KernelFn kernels_rg(const KernelId &id)
 {
-    const int nodes = N + 1;
-    if (tuning().no_full) return {0, 0, nullptr};      /* (msd_tuning("no_full", 1): the general kernels, A/B runs) */
-    if (nodes <= 64) return {64, 1, solve_kernel<64, 1, 1, LOSS_STATIC, false, false, FULL_RG, 1>, false, XCH_FAST, 0, follow_kernel_full_rg(64, 1), solve_kernel<64, 1, 1, LOSS_STATIC, false, false, FULL_RG, 3>};
-    /* (SLDS: the node constants in LDS where they do not cost the fourth resident workgroup of a compute unit -- msd_kernel.hpp: STATIC_FIELDS) */
-    if (MSD_STATIC_LDS && sizeof(double)*(size_t)(lds_doubles(N, 128, false, XCH_FAST, 0) + STATIC_FIELDS*128) <= 40*1024 && nodes > 64)
-        return {64, 2, solve_kernel<64, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1, true>, false, XCH_FAST, 0, follow_kernel_full_rg(64, 2), solve_kernel<64, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3, true>, STATIC_FIELDS*128};
-    if (nodes <= 128) return {64, 2, solve_kernel<64, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1>, false, XCH_FAST, 0, follow_kernel_full_rg(64, 2), solve_kernel<64, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3>};     /* the benchmark geometry */
-    if (nodes <= 256) return {128, 2, solve_kernel<128, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1>, false, XCH_FAST, RED_DOUBLES, follow_kernel_full_rg(128, 2), solve_kernel<128, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3>};
-    /* longer horizons while the five additional exchange arrays still fit the LDS of a compute unit next to the stage blocks */
-    const auto fits = [&](int ns) { return sizeof(double)*(size_t)lds_doubles(N, ns, false, XCH_FAST, RED_DOUBLES) <= 160*1024; };
-    if (nodes <= 384 && fits(384)) return {192, 2, solve_kernel<192, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1>, false, XCH_FAST, RED_DOUBLES, follow_kernel_full_rg(192, 2), solve_kernel<192, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3>};
-    if (nodes <= 512 && fits(512)) return {256, 2, solve_kernel<256, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1>, false, XCH_FAST, RED_DOUBLES, follow_kernel_full_rg(256, 2), solve_kernel<256, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3>};
-    return {0, 0, nullptr};
+    MSD_KERNEL(64, 1, 1, LOSS_STATIC, false, false, FULL_RG, 1)
+    MSD_KERNEL(64, 1, 1, LOSS_STATIC, false, false, FULL_RG, 3)
+    MSD_KERNEL(64, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1, true)
+    MSD_KERNEL(64, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3, true)
+    MSD_KERNEL(64, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1)
+    MSD_KERNEL(64, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3)
+    MSD_KERNEL(128, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1)
+    MSD_KERNEL(128, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3)
+    MSD_KERNEL(192, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1)
+    MSD_KERNEL(192, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3)
+    MSD_KERNEL(256, 2, 1, LOSS_STATIC, false, false, FULL_RG, 1)
+    MSD_KERNEL(256, 2, 1, LOSS_STATIC, false, false, FULL_RG, 3)
+    return nullptr;
 }
 }

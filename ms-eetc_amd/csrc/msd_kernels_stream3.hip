@@ -2,13 +2,17 @@
  * up to 1023 intervals; see msd_geometry.hpp */
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <cstring>
-
 #include "msd_geometry.hpp"
 
 namespace msd {
-Geometry pick_stream_geometry_dynamic(int N) { return N + 1 <= 1024 ? stream_geometry_t<LOSS_TABLE, false, 2>() : Geometry{0, 0, nullptr}; }
-Geometry pick_stream_geometry_general(int N) { return N + 1 <= 1024 ? stream_geometry_t<LOSS_STATIC, true, 2>() : Geometry{0, 0, nullptr}; }
-Geometry pick_stream_geometry_intloss(int N) { return N + 1 <= 1024 ? stream_geometry_t<LOSS_INTEGRATED, false, 2>() : Geometry{0, 0, nullptr}; }
+KernelFn kernels_stream3(const KernelId &id)
+{
+    MSD_KERNEL(512, 2, 2, LOSS_TABLE, true, false, 0, 1)
+    MSD_KERNEL(512, 2, 2, LOSS_TABLE, true, false, 0, 2)
+    MSD_KERNEL(512, 2, 2, LOSS_STATIC, true, true, 0, 1)
+    MSD_KERNEL(512, 2, 2, LOSS_STATIC, true, true, 0, 2)
+    MSD_KERNEL(512, 2, 2, LOSS_INTEGRATED, true, false, 0, 1)
+    MSD_KERNEL(512, 2, 2, LOSS_INTEGRATED, true, false, 0, 2)
+    return nullptr;
+}
 }

@@ -6,6 +6,12 @@
 #include "msd_geometry.hpp"
 
 namespace msd {
-Geometry pick_stream_geometry_general_dynamic(int N) { return N + 1 <= 1024 ? stream_geometry_t<LOSS_TABLE, true, 2>() : Geometry{0, 0, nullptr}; }
-Geometry pick_stream_geometry_general_intloss(int N) { return N + 1 <= 1024 ? stream_geometry_t<LOSS_INTEGRATED, true, 2>() : Geometry{0, 0, nullptr}; }
+KernelFn kernels_stream4(const KernelId &id)
+{
+    MSD_KERNEL(512, 2, 2, LOSS_TABLE, true, true, 0, 1)
+    MSD_KERNEL(512, 2, 2, LOSS_TABLE, true, true, 0, 2)
+    MSD_KERNEL(512, 2, 2, LOSS_INTEGRATED, true, true, 0, 1)
+    MSD_KERNEL(512, 2, 2, LOSS_INTEGRATED, true, true, 0, 2)
+    return nullptr;
+}
 }

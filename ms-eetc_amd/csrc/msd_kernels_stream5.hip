@@ -4,12 +4,12 @@
 #include "msd_geometry.hpp"
 
 namespace msd {
-KernelFn stream_first_pass_full_rg(int SPT)
+KernelFn kernels_stream5(const KernelId &id)
 {
-    if (SPT == 2) return solve_kernel<512, 2, 2, LOSS_STATIC, true, false, FULL_RG, 1>;
-    if (SPT == 4) return solve_kernel<512, 4, 2, LOSS_STATIC, true, false, FULL_RG, 1>;
-    if (SPT == 6) return solve_kernel<512, 6, 2, LOSS_STATIC, true, false, FULL_RG, 1>;
-    if (SPT == 10) return solve_kernel<512, 10, 2, LOSS_STATIC, true, false, FULL_RG, 1>;
+    MSD_KERNEL(512, 2, 2, LOSS_STATIC, true, false, FULL_RG, 1)
+    MSD_KERNEL(512, 4, 2, LOSS_STATIC, true, false, FULL_RG, 1)
+    MSD_KERNEL(512, 6, 2, LOSS_STATIC, true, false, FULL_RG, 1)
+    MSD_KERNEL(512, 10, 2, LOSS_STATIC, true, false, FULL_RG, 1)
     return nullptr;
 }
 }

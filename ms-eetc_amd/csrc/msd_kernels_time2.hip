@@ -5,12 +5,11 @@
 #include "msd_geometry.hpp"
 
 namespace msd {
-Geometry pick_geometry_time_both(int N)
+KernelFn kernels_time2(const KernelId &id)
 {
-    const int nodes = N + 1;
-    if (nodes <= 64) return {64, 1, solve_kernel<64, 1, 1, LOSS_STATIC, false, false, FULL_TIME_BOTH, 1>};
-    if (nodes <= 128) return {64, 2, solve_kernel<64, 2, 1, LOSS_STATIC, false, false, FULL_TIME_BOTH, 1>};
-    if (nodes <= 256) return {128, 2, solve_kernel<128, 2, 1, LOSS_STATIC, false, false, FULL_TIME_BOTH, 1>};
-    return {0, 0, nullptr};
+    MSD_KERNEL(64, 1, 1, LOSS_STATIC, false, false, FULL_TIME_BOTH, 1)
+    MSD_KERNEL(64, 2, 1, LOSS_STATIC, false, false, FULL_TIME_BOTH, 1)
+    MSD_KERNEL(128, 2, 1, LOSS_STATIC, false, false, FULL_TIME_BOTH, 1)
+    return nullptr;
 }
 }

@@ -1,9 +1,11 @@
 /* TEST-ONLY: host emulation, kernel family "integrated losses" (see emu_common.h) */
 #include "emu_common.h"
 
-bool emu_run_intloss(int NT, int SPT, const EmuArgs &a)
+EmuFn emu_kernels_intloss(const msd::KernelId &id)
 {
-    if (NT == 64 && SPT == 1) { run_first_and_follow<64, 1, 2, false, false, 0>(a); return true; }
-    if (NT == 64 && SPT == 2) { run_first_and_follow<64, 2, 2, false, false, 0>(a); return true; }
-    return false;
+    EMU_KERNEL(64, 1, 1, msd::LOSS_INTEGRATED, false, false, 0, 1)
+    EMU_KERNEL(64, 2, 1, msd::LOSS_INTEGRATED, false, false, 0, 1)
+    /* the streamed follow-up kernel of the family */
+    EMU_KERNEL(128, 5, 1, msd::LOSS_INTEGRATED, true, false, 0, 2)
+    return nullptr;
 }

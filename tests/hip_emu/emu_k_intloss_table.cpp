@@ -1,9 +1,11 @@
-/* TEST-ONLY: host emulation, kernel family "integrateLosses with a loss table" (DYN = LOSS_INTEGRATED_TABLE; see emu_common.h) */
+/* TEST-ONLY: host emulation, kernel family "integrateLosses with a loss table" (DYN = LOSS_INTEGRATED_TABLE) (see emu_common.h) */
 #include "emu_common.h"
 
-bool emu_run_intloss_table(int NT, int SPT, const EmuArgs &a)
+EmuFn emu_kernels_intloss_table(const msd::KernelId &id)
 {
-    if (NT == 64 && SPT == 1) { run_first_and_follow<64, 1, msd::LOSS_INTEGRATED_TABLE, false, false, 0>(a); return true; }
-    if (NT == 128 && SPT == 1) { run_first_and_follow<128, 1, msd::LOSS_INTEGRATED_TABLE, false, false, 0>(a); return true; }
-    return false;
+    EMU_KERNEL(64, 1, 1, msd::LOSS_INTEGRATED_TABLE, false, false, 0, 1)
+    EMU_KERNEL(128, 1, 1, msd::LOSS_INTEGRATED_TABLE, false, false, 0, 1)
+    /* the streamed follow-up kernel of the family */
+    EMU_KERNEL(128, 5, 1, msd::LOSS_INTEGRATED_TABLE, true, false, 0, 2)
+    return nullptr;
 }

@@ -1,11 +1,12 @@
 /* TEST-ONLY: host emulation, streamed kernels (see emu_common.h) */
 #include "emu_common.h"
 
-/* full: the first pass with the structure of the rolling stock compiled in (msd_kernels_stream5.hip / 6.hip) */
-bool emu_run_stream(const EmuArgs &a, int full)
+EmuFn emu_kernels_stream(const msd::KernelId &id)
 {
-    if (full == msd::FULL_RG) run_first_and_follow<128, 5, 0, true, false, msd::FULL_RG>(a);
-    else if (full == msd::FULL_BOTH) run_first_and_follow<128, 5, 0, true, false, msd::FULL_BOTH>(a);
-    else run_first_and_follow<128, 5, 0, true, false, 0>(a);
-    return true;
+    /* first pass, also with the structure of the rolling stock compiled in (msd_kernels_stream5.hip / 6.hip), and follow-up kernel */
+    EMU_KERNEL(128, 5, 1, msd::LOSS_STATIC, true, false, msd::FULL_RG, 1)
+    EMU_KERNEL(128, 5, 1, msd::LOSS_STATIC, true, false, msd::FULL_BOTH, 1)
+    EMU_KERNEL(128, 5, 1, msd::LOSS_STATIC, true, false, 0, 1)
+    EMU_KERNEL(128, 5, 1, msd::LOSS_STATIC, true, false, 0, 2)
+    return nullptr;
 }

@@ -406,6 +406,154 @@ def test_emulated_kernel_other_stage_systems(emu, variant):
     assert np.max(np.abs(z[0] - ref['z'])/np.maximum(1, np.abs(ref['z']))) < 1e-7
 
 
+def _selection_case(case):
+    "(train, track, solver options, horizon) of the descriptions the tests above and tests/test_shooting_integrators.py solve in the emulation"
+    from mseetc.train import Train
+    both, rg = cases.train_default, cases.train_fig10
+    if case.startswith('static'):
+        N = int(case.split('N')[1])
+        return (both() if 'both' in case else rg()), (cases.track_00(16000) if N == 40 else cases.track_00()), {}, N
+    if case == 'time_optimal':
+        return cases.train_fig5(), cases.track_00(8500), dict(energyOptimal=False), 30
+    if case == 'loss_table':
+        from mseetc.efficiency import totalLossesFunction
+        train = Train(config={'id': 'NL_Intercity_VIRM6'})
+        train.forceMinPn = 0
+        train.powerLosses = totalLossesFunction(train, auxiliaries=27000, etaGear=0.96)
+        return train, cases.track_00(8500), {}, 30
+    if case == 'integrateLosses':
+        return both(), cases.track_00(12000), dict(integrateLosses=True), 30
+    if case == 'collocation':
+        return both(), cases.track_00(12000), dict(integrationMethod='IRK', integrationOptions=dict(order=2, numSteps=1, numApproxSteps=0)), 30
+    assert case == 'streamed'
+    return both(), cases.track_00(), {}, 150
+
+
+def _kernel_id(symbol):
+    "the template arguments of a solve_kernel symbol: (NT, SPT, WPS, DYN, STREAM, GEN, FULL, PART, SLDS, SOCK)"
+    import re
+    args = re.match(r'_ZN3msd12solve_kernelI((?:L[ib]\d+E)+)E', symbol).group(1)
+    return tuple(int(v) for v in re.findall(r'L[ib](\d+)E', args))
+
+
+# Where the emulation does not compile the instantiation the library picks (tests/hip_emu/emu_k_*.cpp hold fewer kernels than msd_kernels_*.hip):
+# (case, kernel) -> (the library's, the emulation's instead).  A first pass: the next rung of the ladder (msd_select.hpp).
+#   static_*_N100      no fused first pass with the node constants in LDS (SLDS) but the one with the second-order correction inside: the plain 64 x 2 kernel
+#   static_rg_N40      no 64 x 1 follow-up kernel: the ladder lets the 64 x 2 one follow up, as in the library's both-brakes family
+#   integrateLosses,
+#   collocation        none of these families' kernels with both brakes compiled in (msd_kernels_full2.hip): the general kernel of the same geometry
+EMU_LACKS = {
+    ('static_both_N100', 'first'): ((64, 2, 1, 0, 0, 0, 1, 1, 1, 0), (64, 2, 1, 0, 0, 0, 1, 1, 0, 0)),
+    ('static_rg_N100', 'first'): ((64, 2, 1, 0, 0, 0, 2, 1, 1, 0), (64, 2, 1, 0, 0, 0, 2, 1, 0, 0)),
+    ('static_rg_N40', 'follow'): ((64, 1, 1, 0, 0, 0, 2, 2, 0, 0), (64, 2, 1, 0, 0, 0, 2, 2, 0, 0)),
+    ('integrateLosses', 'first'): ((64, 1, 1, 2, 0, 0, 1, 1, 0, 0), (64, 1, 1, 2, 0, 0, 0, 1, 0, 0)),
+    ('collocation', 'first'): ((64, 1, 1, 0, 0, 1, 1, 1, 0, 0), (64, 1, 1, 0, 0, 1, 0, 1, 0, 0)),
+}
+
+
+@pytest.mark.parametrize('case', ['static_both_N40', 'static_both_N100', 'static_rg_N40', 'static_rg_N100', 'time_optimal', 'loss_table', 'integrateLosses',
+                                  'collocation', 'streamed'])
+def test_emulation_runs_the_kernels_the_library_selects(emu, case, monkeypatch):
+    """
+    The emulation picks its kernels through the library's ladder (msd_select.hpp) and reports the ids of the ones its last call ran (emu_last_kernels, in
+    the ladder's terms: a streamed kernel under the library's geometry, which the emulation runs on its 128 x 5 stand-in).  First pass and follow-up kernel
+    are the ones msd_plan_describe names for the same description; the differences are the list EMU_LACKS, anything else fails.  `streamed`: EMU_GEOMETRY=stream
+    runs the long-horizon kernels at a horizon the library keeps LDS-resident, so the plan to compare with is that of the same train and track at 700
+    intervals.  Three iterations per attempt: which kernels run does not depend on the iteration limit.  (Not part of the sanitizer runs, which select the tests
+    named `emulated`: the MemorySanitizer build runs in a process of its own and keeps no record of its last call.)
+    """
+    from mseetc.ocp import casadiSolver
+    from mseetc import _device
+    from mseetc._device import ST
+    train, track, extra, N = _selection_case(case)
+    opts = dict(dict(numIntervals=N, maxIterations=3, integrationOptions=dict(numSteps=1, numApproxSteps=1)), **extra)
+    solver = casadiSolver(train, track, opts, startingPoint='profile')
+    described = solver
+    if case == 'streamed':
+        monkeypatch.setenv('EMU_GEOMETRY', 'stream')
+        described = casadiSolver(train, track, dict(opts, numIntervals=700), startingPoint='profile')
+    buf = ctypes.create_string_buffer(4096)
+    _device._check(_device.lib().msd_plan_describe(ctypes.byref(described._desc), buf, len(buf)))
+    plan = dict(f.split('=', 1) for f in buf.value.decode().split())
+    first, follow = _kernel_id(plan['kernel']), _kernel_id(plan['kernel2'])
+    if case == 'streamed':
+        assert plan['stream'] == '1'
+
+    scen = solver._scenarios(1541.0, 0, 1, 1)
+    nz = (4 + int(solver.withPnBrake))*N + 2
+    z, lam, st, hist = np.zeros((1, nz)), np.zeros((1, 7*N)), np.zeros((1, ST['COUNT'])), np.zeros((8, 8))
+    d = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    assert emu.emu_solve_batch(ctypes.byref(solver._desc), 1, d(scen), d(z), d(lam), d(st), d(hist), 8) == 0
+    ran = _last_kernels(emu)
+    print(case, plan['kernel'], plan['kernel2'], ran)
+    for kernel, selected in (('first', first), ('follow', follow)):
+        assert selected[0] != 0
+        if (case, kernel) in EMU_LACKS:
+            assert selected == EMU_LACKS[case, kernel][0]
+            selected = EMU_LACKS[case, kernel][1]
+        assert ran[kernel] == selected, (kernel, ran[kernel], selected)
+
+
+def _last_kernels(emu):
+    "the ids emu_last_kernels reports: dict(first=..., follow=...) of 10-tuples (NT = 0: none ran)"
+    emu.emu_last_kernels.restype = ctypes.c_char_p
+    return {k: tuple(int(x) for x in v.split(',')) for k, v in (f.split('=') for f in emu.emu_last_kernels().decode().split())}
+
+
+@pytest.mark.parametrize('geometry,first,follow', [
+    # a kernel no horizon gets (the library's unit keeps it as MSD_KERNEL_UNUSED): the general 128 x 1 kernel of the static loss model, the streamed kernel follows up
+    ('128x1', (128, 1, 1, 0, 0, 0, 0, 1, 0, 0), (512, 2, 2, 0, 1, 0, 0, 2, 0, 0)),
+    # structured kernels first: the fused 128 x 2 pair with both brakes
+    ('128x2', (128, 2, 1, 0, 0, 0, 1, 1, 0, 0), (128, 2, 1, 0, 0, 0, 1, 2, 0, 0)),
+    ('192x2', (192, 2, 1, 0, 0, 0, 0, 1, 0, 0), (512, 2, 2, 0, 1, 0, 0, 2, 0, 0))])
+def test_emulated_forced_geometry_runs_that_geometry(emu, geometry, first, follow, monkeypatch):
+    """
+    EMU_GEOMETRY=NTxSPT runs the family's kernel of that geometry whatever the horizon, a structured one where the emulation compiles it -- also a
+    geometry that no horizon of the family gets.  N = 40 with both brakes: the ids that ran, and the optimum of the geometry the horizon gets by itself
+    (64 x 1).  Both runs converge to the tolerance 1e-8 of the scaled problem; 1e-6 relative on the point is the bound of the one-brake test above for
+    two runs that may stop a barrier reduction apart.
+    """
+    from mseetc.ocp import casadiSolver
+    from mseetc._device import ST
+    N, T = 40, 804.0
+    solver = casadiSolver(cases.train_default(), cases.track_00(16000), dict(numIntervals=N, maxIterations=300, integrationOptions=dict(numSteps=1, numApproxSteps=1)),
+                          startingPoint='profile')
+    scen = solver._scenarios(T, 0, 1, 1)
+    d = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    runs = []
+    for force in (None, geometry):
+        if force:
+            monkeypatch.setenv('EMU_GEOMETRY', force)
+        z, lam, st, hist = np.zeros((1, 5*N + 2)), np.zeros((1, 7*N)), np.zeros((1, ST['COUNT'])), np.zeros((8, 8))
+        assert emu.emu_solve_batch(ctypes.byref(solver._desc), 1, d(scen), d(z), d(lam), d(st), d(hist), 8) == 0
+        assert st[0, ST['STATUS']] == 0
+        runs.append((z, st))
+    if hasattr(emu, 'emu_last_kernels'):      # (not the MemorySanitizer proxy: a process per call)
+        assert _last_kernels(emu) == dict(first=first, follow=follow)
+    assert abs(runs[1][1][0, ST['OBJ']] - runs[0][1][0, ST['OBJ']]) <= 1e-8*abs(runs[0][1][0, ST['OBJ']])
+    assert np.max(np.abs(runs[1][0] - runs[0][0])/np.maximum(1, np.abs(runs[0][0]))) < 1e-6
+
+
+def test_emulated_sock_override_leaves_the_launch_behind_the_estimate_alone(emu, monkeypatch):
+    """
+    EMU_SOCK=1 swaps the plain first pass only.  From the reference's starting point the launch needs the least-squares multiplier estimate: N = 100 with both
+    brakes runs the plain 64 x 2 first pass behind the estimate (PART = 3; the emulation has no SLDS one) and the follow-up kernel, as without the switch.
+    """
+    from mseetc.ocp import casadiSolver
+    from mseetc._device import ST
+    monkeypatch.setenv('EMU_SOCK', '1')
+    N = 100
+    solver = casadiSolver(cases.train_default(), cases.track_00(), dict(numIntervals=N, maxIterations=3, integrationOptions=dict(numSteps=1, numApproxSteps=1)),
+                          startingPoint='reference')
+    scen = solver._scenarios(1541.0, 0, 1, 1)
+    z, lam, st, hist = np.zeros((1, 5*N + 2)), np.zeros((1, 7*N)), np.full((1, ST['COUNT']), -77.0), np.zeros((8, 8))
+    d = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    assert emu.emu_solve_batch(ctypes.byref(solver._desc), 1, d(scen), d(z), d(lam), d(st), d(hist), 8) == 0
+    assert st[0, ST['STATUS']] != -77.0
+    if hasattr(emu, 'emu_last_kernels'):
+        assert _last_kernels(emu) == dict(first=(64, 2, 1, 0, 0, 0, 1, 3, 0, 0), follow=(64, 2, 1, 0, 0, 0, 1, 2, 0, 0))
+
+
 @pytest.mark.skipif(not __import__('os').environ.get('RUN_SANITIZERS'), reason="opt-in (several minutes): RUN_SANITIZERS=1")
 def test_emulation_under_sanitizers():
     "ASan + UBSan over the emulated kernel (all emulation tests, every geometry they use): tests/hip_emu/run_sanitizers.sh must pass."
