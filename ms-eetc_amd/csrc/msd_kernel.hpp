@@ -545,6 +545,13 @@ template <class Op> __device__ __forceinline__ double wave_reduce(double x, Op o
 }
 #endif
 
+/* a flag of any lane of the wave, as a scalar: one compare into a lane mask instead of a reduction */
+#ifndef MSD_HOST_EMULATION
+__device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
+#else
+__device__ __forceinline__ bool wave_any(bool p) { return wave_reduce(p ? 1.0 : 0.0, OpMax()) != 0.0; }
+#endif
+
 template <int K, class Op> __device__ __forceinline__ void block_reduce(double (&v)[K], Op op, Ctx &c)
 {
 #pragma unroll
@@ -766,6 +773,29 @@ __device__ __forceinline__ double uni(double v)
     int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
     int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
     return __hiloint2double(hi, lo);
+}
+
+/* a flag of any thread of the workgroup, uniform: a ballot on a single wave */
+__device__ __forceinline__ bool block_any(bool p, Ctx &c)
+{
+    if (c.nw == 1) return wave_any(p);
+    double v[1] = {p ? 1.0 : 0.0};
+    block_reduce<1>(v, OpMax(), c);
+    return uni(v[0]) != 0.0;
+}
+
+/* K sums and a flag of any thread: the flag is a ballot on a single wave and rides along as one more term otherwise (one barrier for both) */
+template <int K> __device__ __forceinline__ bool block_sum_any(double (&v)[K], bool p, Ctx &c)
+{
+    if (c.nw == 1) { block_reduce<K>(v, OpSum(), c); return wave_any(p); }
+    double w[K + 1];
+#pragma unroll
+    for (int k = 0; k < K; k++) w[k] = v[k];
+    w[K] = p ? 1.0 : 0.0;
+    block_reduce<K + 1>(w, OpSum(), c);
+#pragma unroll
+    for (int k = 0; k < K; k++) v[k] = w[k];
+    return uni(w[K]) != 0.0;
 }
 
 /* derivatives of the interval map kept between the evaluation and the KKT assembly */
@@ -1498,9 +1528,12 @@ struct ParallelRiccati {
             }
         }
         c.mark(PH_R_ELEM);
+        /* Depth of the three scans.  nact = chunks with stages in the fullest wave (wave 0; uniform over the workgroup): a lane has a partner at distance
+         * d only if d < nact, so the levels from there on would change nothing and are not run */
+        const int nact = wg_uniform((N - 1 + SPT - 1)/SPT > 64 ? 64 : (N - 1 + SPT - 1)/SPT);
         /* ---- 2: suffix scan over the lanes of the wave, then over the waves ---- */
 #pragma unroll 1
-        for (int d = 1; d < 64; d <<= 1) {
+        for (int d = 1; d < nact; d <<= 1) {
             double mine[21], theirs[21];
             pack_elem(agg, mine);
             wave_fetch<21>(mine, theirs, c.lane + d);
@@ -1608,11 +1641,14 @@ struct ParallelRiccati {
             }
         }
         /* ---- inertia and breakdown flags (uniform from here) ---- */
-        {
+        if (c.nw == 1) {      /* one wave: two ballots */
+            if (wave_any(bad)) return -1;
+            if (wave_any(!ok)) return 0;
+        } else {
             double v[2] = {ok ? 0.0 : 1.0, bad ? 1.0 : 0.0};
-            if (c.nw > 1) __syncthreads();      /* the wave totals of the scan share the reduction scratch */
+            __syncthreads();      /* the wave totals of the scan share the reduction scratch */
             block_reduce<2>(v, OpMax(), c);
-            if (c.nw > 1) __syncthreads();
+            __syncthreads();
             if (uni(v[1]) != 0.0) return -1;
             if (uni(v[0]) != 0.0) return 0;
         }
@@ -1620,7 +1656,7 @@ struct ParallelRiccati {
         c.mark(PH_R_RECUR);
         /* ---- 4: suffix scan of the gradient maps ---- */
 #pragma unroll 1
-        for (int d = 1; d < 64; d <<= 1) {
+        for (int d = 1; d < nact; d <<= 1) {
             double mine[12], theirs[12];
             pack_aff(bmap, mine);
             wave_fetch<12>(mine, theirs, c.lane + d);
@@ -1690,7 +1726,7 @@ struct ParallelRiccati {
         c.mark(PH_R_FEED);
         /* ---- 6: prefix scan of the closed-loop maps ---- */
 #pragma unroll 1
-        for (int d = 1; d < 64; d <<= 1) {
+        for (int d = 1; d < nact; d <<= 1) {
             double mine[12], theirs[12];
             pack_aff(fmap, mine);
             wave_fetch<12>(mine, theirs, c.lane - d);
@@ -2629,10 +2665,10 @@ struct Solver {
             lsum.add(prod);
         }
         logs = lsum.value();
-        double v[5] = {th, logs, damp, obj, bad};
-        block_reduce<5>(v, OpSum(), c);
+        double v[4] = {th, logs, damp, obj};
+        const bool anybad = block_sum_any<4>(v, bad != 0, c);
         theta = uni(v[0]); phi = uni(v[3] - mu_*v[1] + K_D*mu_*v[2]);
-        ok = (uni(v[4]) == 0.0) && isfinite(theta) && isfinite(phi);
+        ok = !anybad && isfinite(theta) && isfinite(phi);
     }
 
     /* c and d - sigma at the trial point x + alpha d (needed by the second-order correction only) */
@@ -3346,11 +3382,11 @@ struct Solver {
             }
             lsum.add(prod);
         }
-        double v[5] = {th, lsum.value(), damp, obj, bad};
-        block_reduce<5>(v, OpSum(), c);
+        double v[4] = {th, lsum.value(), damp, obj};
+        const bool anybad = block_sum_any<4>(v, bad != 0, c);
         T.theta = uni(v[0]); T.L = uni(v[1]); T.D = uni(v[2]); T.obj = uni(v[3]);
         phi = T.obj - mu_*T.L + K_D*mu_*T.D;
-        ok = (uni(v[4]) == 0.0) && isfinite(T.theta) && isfinite(phi);
+        ok = !anybad && isfinite(T.theta) && isfinite(phi);
     }
 
     /* accept x + alpha d (the point merit_fast published); multipliers like the general path's update.  The safeguard that keeps
@@ -3411,9 +3447,7 @@ struct Solver {
                 nd.lam[0] += apr*(dd.lt - nd.lam[0]); nd.lam[1] += apr*(dd.lb - nd.lam[1]);
             }
         }
-        double v[1] = {clamp ? 1.0 : 0.0};
-        block_reduce<1>(v, OpMax(), c);
-        if (uni(v[0]) != 0.0) {
+        if (block_any(clamp, c)) {
             /* (every index a compile-time constant: a run-time index into the nodes' fields would move the whole iterate into scratch memory) */
 #pragma unroll
             for (int j = 0; j < SPT; j++) {

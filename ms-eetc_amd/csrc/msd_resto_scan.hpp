@@ -274,9 +274,11 @@ struct ParallelResto {
                 have = true;
             }
         }
+        /* chunks with stages in the fullest wave: no lane has a partner at a distance d >= nact (ParallelRiccati::solve) */
+        const int nact = wg_uniform((N - 1 + SPT - 1)/SPT > 64 ? 64 : (N - 1 + SPT - 1)/SPT);
         /* ---- 2: suffix scan over the lanes of the wave, then over the waves ---- */
 #pragma unroll 1
-        for (int d = 1; d < 64; d <<= 1) {
+        for (int d = 1; d < nact; d <<= 1) {
             double mine[21], theirs[21];
             PR::pack_elem(agg, mine);
             wave_fetch<21>(mine, theirs, c.lane + d);
@@ -371,7 +373,7 @@ struct ParallelResto {
 
         /* ---- 4: suffix scan of the gradient maps ---- */
 #pragma unroll 1
-        for (int d = 1; d < 64; d <<= 1) {
+        for (int d = 1; d < nact; d <<= 1) {
             double mine[12], theirs[12];
             PR::pack_aff(bmap, mine);
             wave_fetch<12>(mine, theirs, c.lane + d);
@@ -451,7 +453,7 @@ struct ParallelResto {
         }
         /* ---- 6: prefix scan of the closed-loop maps ---- */
 #pragma unroll 1
-        for (int d = 1; d < 64; d <<= 1) {
+        for (int d = 1; d < nact; d <<= 1) {
             double mine[12], theirs[12];
             PR::pack_aff(fmap, mine);
             wave_fetch<12>(mine, theirs, c.lane - d);
