@@ -195,8 +195,9 @@ int msd_problem_geometry(msd_handle h, int *threads_per_scenario, int *nodes_per
  * device memory -- in the reference all of that is inside the one call of IPOPT (ocp.py:359).
  * Telemetry, never reset: counts[0] scenarios handed over since the handle was created, counts[1 + why] by reason (0 no fused start for the
  * scenario, 1 wrong inertia or scan breakdown, 2 tiny step, 3 rejected first trial point with a second-order correction due, 4 line search
- * broke down, 5 breakdown that asks for the second attempt, 6 ten shortened iterations in a row: the watchdog procedure is due).  Waits for the
- * handle's stream.  n <= 8 entries are written.
+ * broke down, 5 breakdown that asks for the second attempt, 6 ten shortened iterations in a row: the watchdog procedure is due, 7 the iteration
+ * budget of the first pass ran out: msd_problem_iteration_budget).  Waits for the handle's stream.  n <= 9 entries are written; a caller that asks
+ * for 8 gets the total and reasons 0 ... 6.
  */
 int msd_problem_follow_counts(msd_handle h, int *counts, int n);
 
@@ -244,6 +245,43 @@ int msd_synchronize(msd_handle h);
  */
 int msd_solve_batch_multi(const msd_handle *handles, int nhandles, int nscen, const double *scen, const double *overrides, const double *z_guess,
                           double mu_init, double bound_push, double *z_out, double *lam_out, double *stats, float *kernel_ms);
+
+/*
+ * Early results: the scenarios of a batch that have ended are readable while the stragglers still run.  One scenario without a solution keeps
+ * its launch busy until the iteration limit; the reference's solves are separate calls (a failed one returns None, ocp.py:364-370), so a caller
+ * there never waits for a scenario it did not ask about.  Opt-in per handle; without these calls nothing changes.
+ *
+ *   msd_problem_early_results(h, on)   the handle allocates and owns one completion word (int) and one mirror of the stats record per scenario,
+ *                                      in host memory the device can write; both grow with the largest batch.  Default off.
+ *   msd_problem_iteration_budget(h, k) k > 0: a first pass spends at most k iterations on a scenario, then hands it over (reason 7 of
+ *                                      msd_problem_follow_counts) to the follow-up kernel, which solves it from its starting point under the
+ *                                      problem's own max_iterations -- a crawling scenario then does not occupy the first pass until that limit.
+ *                                      0 (default): none, results bit for bit as before.  Negative: MSD_E_INVALID.  Holds for every launch of the
+ *                                      handle that has a follow-up kernel behind its first pass.
+ *   msd_solve_batch_begin(...)         msd_solve_batch_ex without the wait: uploads, enqueues both kernels and the copy of the stats records, returns.
+ *                                      Needs early results on.  z_out, lam_out (if given) and stats must be page-locked (msd_host_alloc,
+ *                                      hipHostMalloc, hipHostRegister): the kernels store z* and the multipliers there themselves.  MSD_E_INVALID
+ *                                      otherwise, and while a begun batch has not been waited for with MSD_WAIT_ALL.  The completion words are zeroed
+ *                                      before the launch.
+ *   msd_solve_batch_wait(h, what, &n)  MSD_WAIT_FIRST_PASS: until the first of the two kernels has ended; n = scenarios whose word is still 0 (they
+ *                                      are the follow-up kernel's, which may have ended some by the time the caller looks).  MSD_WAIT_ALL: until
+ *                                      everything has ended and `stats` holds the final records; n = 0; the handle is free for the next batch.
+ *   msd_solve_batch_done(h, &w, &s)    host addresses of the completion words [nscen] and of the stats mirror [nscen][MSD_ST_COUNT] (valid until the
+ *                                      next msd_solve_batch_begin with a larger batch, or msd_problem_destroy): a caller polls them without any HIP call.
+ *
+ * Word of a scenario: 0 not ended yet, 1 ended by the first pass, 2 ended by the follow-up kernel.  Guarantee: once a scenario's word reads non-zero,
+ * its rows of z_out, lam_out and of the stats mirror are final (the word is stored behind them with release ordering at system scope; read it with
+ * acquire ordering, or through the volatile pointer followed by a fence).  The rows of a scenario whose word is 0 are unspecified.
+ * Not combined with msd_problem_keep_duals, msd_solve_batch_shifted, msd_solve_batch_multi or the loops of mseetc_mpc.h: between begin and
+ * MSD_WAIT_ALL every other solve of the handle returns MSD_E_INVALID, and so does begin on a handle that keeps its duals.
+ */
+#define MSD_WAIT_FIRST_PASS 1
+#define MSD_WAIT_ALL 2
+int msd_problem_early_results(msd_handle h, int on);
+int msd_problem_iteration_budget(msd_handle h, int budget);
+int msd_solve_batch_begin(msd_handle h, int nscen, const double *scen, const double *overrides, double *z_out, double *lam_out, double *stats);
+int msd_solve_batch_wait(msd_handle h, int what, int *n_pending);
+int msd_solve_batch_done(msd_handle h, const volatile int **words, const double **stats_now);
 
 /*
  * The other two interval integrators of TrainIntegrator (mseetc/train.py:303-322) for n independent intervals -- what

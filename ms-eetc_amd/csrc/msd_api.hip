@@ -242,6 +242,7 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
     P.guess = ws.d_guess; P.guessStride = ws.stride; P.guessStatus = ws.d_status; P.warmMu = ws.mu; P.warmPush = ws.push;
     P.dualIn = ws.d_dual_in; P.dualInStride = ws.dual_stride; P.dualShift = ws.dual_shift; P.dualOut = ws.d_dual_out;
     P.oneAttempt = ws.one_attempt ? 1 : 0;
+    P.done = ws.d_done; P.statsHost = ws.d_stats_host; P.budget = ws.budget;
     const bool split = pl.kernel2 != nullptr;
     const bool plain = !pl.fused_family || (ws.d_guess ? ws.d_dual_in != nullptr : P.start == MSD_START_PROFILE);      /* no multiplier estimate needed */
     const bool first_pass = split && (plain || pl.kernel_lsq != nullptr);
@@ -430,6 +431,7 @@ int msd_problem_create(const msd_problem_desc *d, int device, msd_handle *out)
 int msd_problem_reconfigure(msd_handle h, const msd_problem_desc *d)
 {
     if (!h || !d) return fail(MSD_E_INVALID, "null argument");
+    if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
     /* Whatever rejects the description or fails on the way (check_desc, the selection of a plan, a HIP call), the handle holds no problem afterwards:
      * its solves fail with "the handle holds no problem" until a reconfiguration succeeds.  Stream, events and buffers are kept */
     int rc = check_desc(d);
@@ -443,11 +445,15 @@ int msd_problem_destroy(msd_handle h)
     if (!h) return MSD_OK;
     if (h->attached_loops > 0) return fail(MSD_E_INVALID, "a receding-horizon loop (msd_mpc_create) still runs on this handle: destroy the loop first");
     hipSetDevice(h->device);
+    if (h->begun) hipStreamSynchronize(h->stream);      /* (a begun batch nobody waited for: its kernels write the words and the mirror freed below) */
     hipFree(h->d_prof); hipFree(h->d_loss); hipFree(h->d_work); hipFree(h->d_queue); hipFree(h->d_follow);
     hipFree(h->d_scen); hipFree(h->d_ovr); hipFree(h->d_z); hipFree(h->d_lam); hipFree(h->d_stats); hipFree(h->d_hist); hipFree(h->d_guess); hipFree(h->d_eval);
     hipFree(h->d_z2); hipFree(h->d_stats2); hipFree(h->d_dual); hipFree(h->d_dual2); hipFree(h->d_coll);
     if (h->h_stage) hipHostFree(h->h_stage);
     if (h->h_soc_seen) hipHostFree((void *)h->h_soc_seen);
+    if (h->h_done) hipHostFree((void *)h->h_done);
+    if (h->h_stats_now) hipHostFree(h->h_stats_now);
+    if (h->ev_first) hipEventDestroy(h->ev_first);
     for (int k = 0; k < msd_problem::FP_RING; k++) { if (h->fp_beg[k]) hipEventDestroy(h->fp_beg[k]); if (h->fp_end[k]) hipEventDestroy(h->fp_end[k]); }
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -474,6 +480,7 @@ static int launch(msd_handle h, int nscen, const double *d_scen, const double *d
      * then on (msd_kernel.hpp: SOCK; 4 % slower per iteration, no tail); the kernels report it through a word of mapped host memory, read here without
      * waiting for anything */
     WarmStart ws = ws_in;
+    ws.budget = h->budget;
     if (h->plan.kernel_soc) {
         ws.d_soc_seen = h->d_soc_seen;
         if (*h->h_soc_seen != 0) ws.use_soc = true;
@@ -497,12 +504,13 @@ static int launch(msd_handle h, int nscen, const double *d_scen, const double *d
     int *queue = h->d_queue + h->queue_slot;
     h->queue_slot = (h->queue_slot + 1) % QUEUE_RING;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->time_first_pass) {
+    if (h->time_first_pass && !ws.d_done) {
         const int k = (int)(h->fp_count % msd_problem::FP_RING);
         if (!h->fp_beg[k]) { HIP_TRY(hipEventCreate(&h->fp_beg[k])); HIP_TRY(hipEventCreate(&h->fp_end[k])); }
         e0 = h->fp_beg[k]; e1 = h->fp_end[k];
         h->fp_count++;
     }
+    if (ws.d_done) e1 = h->ev_first;      /* a begun batch: MSD_WAIT_FIRST_PASS waits for an event of its own behind the first kernel */
 #ifdef MSD_DEBUG_HOOKS      /* (diagnostic builds: the device buffers of a launch, to place the address of a memory fault) */
     if (getenv("MSD_DEBUG_PTRS"))
         fprintf(stderr, "[msd] launch nscen %d  work %p (+%zu B)  follow %p  queue %p  prof %p  scen %p  z %p  lam %p  stats %p  hist %p  %s  grid caps %d %d %d\n",
@@ -520,6 +528,7 @@ int msd_solve_batch_device(msd_handle h, int nscen, const double *d_scen, double
 int msd_solve_batch_device_ex(msd_handle h, int nscen, const double *d_scen, const double *d_overrides, double *d_z, double *d_lam, double *d_stats)
 {
     if (!h || nscen < 1 || !d_scen || !d_z || !d_stats) return fail(MSD_E_INVALID, "bad argument");
+    if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
     HIP_TRY(hipSetDevice(h->device));
     return launch(h, nscen, d_scen, d_overrides, d_z, d_lam, d_stats, nullptr, 0);
 }
@@ -535,9 +544,9 @@ int msd_problem_follow_counts(msd_handle h, int *counts, int n)
 {
     if (!h || !counts || n < 1) return fail(MSD_E_INVALID, "bad argument");
 #ifdef MSD_DEBUG_HOOKS
-    if (n > 8 && !(getenv("MSD_DEBUG_NO_FOLLOW_UP") && *getenv("MSD_DEBUG_NO_FOLLOW_UP") == '1')) n = 8;      /* (diagnostic builds: the list's entries behind the counters) */
+    if (n > 9 && !(getenv("MSD_DEBUG_NO_FOLLOW_UP") && *getenv("MSD_DEBUG_NO_FOLLOW_UP") == '1')) n = 9;      /* (diagnostic builds: the list's entries behind the counters) */
 #else
-    if (n > 8) n = 8;
+    if (n > 9) n = 9;
 #endif
     if (n > (int)h->cap_follow - msd::FOLLOW_TOTAL && h->d_follow) n = (int)h->cap_follow - msd::FOLLOW_TOTAL;
     for (int k = 0; k < n; k++) counts[k] = 0;
@@ -596,6 +605,7 @@ static int check_batch(msd_handle h, int nscen, const double *scen, const double
                        const double *z_out, const double *stats)
 {
     if (!h || nscen < 1 || !scen || !z_out || !stats) return fail(MSD_E_INVALID, "bad argument");
+    if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
     if (z_guess && (!(mu_init > 0) || !(mu_init <= 1e3) || !(bound_push > 0) || !(bound_push <= 0.5)))
         return fail(MSD_E_INVALID, "warm start needs 0 < mu_init <= 1e3 and 0 < bound_push <= 0.5");
     if (overrides)
@@ -650,7 +660,7 @@ static int enqueue_downloads(msd_handle h, int nscen, double *z_out, double *lam
  * defer_downloads: the caller issues enqueue_downloads() itself -- a copy into pageable host memory holds the calling thread until the
  * kernel in front of it has finished, so a caller that drives several devices launches on all of them first */
 static int enqueue_batch(msd_handle h, int nscen, const double *scen, const double *overrides, const double *z_guess, double mu_init, double bound_push,
-                         double *z_out, double *lam_out, double *stats, int shift = -1, bool defer_downloads = false)
+                         double *z_out, double *lam_out, double *stats, int shift = -1, bool defer_downloads = false, bool early = false)
 {
     HIP_TRY(hipSetDevice(h->device));
     const size_t nz = h->plan.nz;
@@ -717,7 +727,12 @@ static int enqueue_batch(msd_handle h, int nscen, const double *scen, const doub
      * tools/zero_copy_probe.py).  The status records stay on the device (the follow-up kernel reads them) and are copied */
     double *kz = h->d_z, *kl = lam_out ? h->d_lam : nullptr;
     h->last_direct = false;
-    if (h->direct_results && shift < 0 && !h->keep_duals) {      /* (keep_duals: a shifted re-solve is to follow, the solutions stay with the multipliers) */
+    if (early) {
+        /* msd_solve_batch_begin: the caller reads a scenario's rows as soon as its completion word is set, so the kernels store them in the caller's
+         * arrays themselves, whatever msd_problem_direct_results says (the caller has checked that the device can address the arrays) */
+        kz = device_address(z_out); kl = lam_out ? device_address(lam_out) : nullptr; h->last_direct = true;
+        ws.d_done = h->d_done; ws.d_stats_host = h->d_stats_now;
+    } else if (h->direct_results && shift < 0 && !h->keep_duals) {      /* (keep_duals: a shifted re-solve is to follow, the solutions stay with the multipliers) */
         double *dz = device_address(z_out), *dl = lam_out ? device_address(lam_out) : nullptr;
         if (dz && (!lam_out || dl)) { kz = dz; kl = dl; h->last_direct = true; }
     }
@@ -748,6 +763,73 @@ int msd_solve_batch_warm(msd_handle h, int nscen, const double *scen, const doub
     rc = enqueue_batch(h, nscen, scen, overrides, z_guess, mu_init, bound_push, z_out, lam_out, stats);
     if (rc != MSD_OK) return rc;
     return finish_batch(h, kernel_ms);
+}
+
+int msd_problem_early_results(msd_handle h, int on)
+{
+    if (!h) return fail(MSD_E_INVALID, "null handle");
+    if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
+    h->early_results = on != 0;      /* (the words and the mirror are allocated by the first msd_solve_batch_begin and kept) */
+    return MSD_OK;
+}
+
+int msd_problem_iteration_budget(msd_handle h, int budget)
+{
+    if (!h) return fail(MSD_E_INVALID, "null handle");
+    if (budget < 0) return fail(MSD_E_INVALID, "the iteration budget of the first pass must not be negative (0: none)");
+    h->budget = budget;
+    return MSD_OK;
+}
+
+int msd_solve_batch_begin(msd_handle h, int nscen, const double *scen, const double *overrides, double *z_out, double *lam_out, double *stats)
+{
+    if (!h) return fail(MSD_E_INVALID, "bad argument");
+    if (!h->early_results) return fail(MSD_E_INVALID, "msd_solve_batch_begin needs early results switched on (msd_problem_early_results)");
+    if (h->keep_duals) return fail(MSD_E_INVALID, "early results are not combined with msd_problem_keep_duals");
+    int rc = check_batch(h, nscen, scen, overrides, nullptr, 0.0, 0.0, z_out, stats);      /* (also: no batch begun and not waited for) */
+    if (rc != MSD_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    if (!device_address(z_out) || (lam_out && !device_address(lam_out)) || !device_address(stats))
+        return fail(MSD_E_INVALID, "msd_solve_batch_begin: z_out, lam_out and stats must be page-locked (msd_host_alloc, hipHostMalloc, hipHostRegister)");
+    if (!h->ev_first) HIP_TRY(hipEventCreate(&h->ev_first));
+    if (nscen > h->cap_done) {
+        /* (no launch of the handle is in flight: every other solve waits for its own, and the previous begun batch has been waited for) */
+        if (h->h_done) hipHostFree((void *)h->h_done);
+        if (h->h_stats_now) hipHostFree(h->h_stats_now);
+        h->h_done = nullptr; h->d_done = nullptr; h->h_stats_now = h->d_stats_now = nullptr; h->cap_done = 0;
+        HIP_TRY(hipHostMalloc((void **)&h->h_done, sizeof(int)*(size_t)nscen, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void **)&h->d_done, (void *)h->h_done, 0));
+        HIP_TRY(hipHostMalloc((void **)&h->h_stats_now, sizeof(double)*MSD_ST_COUNT*(size_t)nscen, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void **)&h->d_stats_now, (void *)h->h_stats_now, 0));
+        h->cap_done = nscen;
+    }
+    for (int k = 0; k < nscen; k++) h->h_done[k] = 0;
+    rc = enqueue_batch(h, nscen, scen, overrides, nullptr, 0.0, 0.0, z_out, lam_out, stats, -1, false, true);
+    if (rc != MSD_OK) { hipStreamSynchronize(h->stream); return rc; }      /* (whatever was enqueued before the failure has ended when the caller frees its arrays) */
+    h->begun = nscen;
+    return MSD_OK;
+}
+
+int msd_solve_batch_wait(msd_handle h, int what, int *n_pending)
+{
+    if (!h || (what != MSD_WAIT_FIRST_PASS && what != MSD_WAIT_ALL)) return fail(MSD_E_INVALID, "bad argument");
+    if (!h->begun) return fail(MSD_E_INVALID, "no batch has been begun (msd_solve_batch_begin)");
+    HIP_TRY(hipSetDevice(h->device));
+    if (what == MSD_WAIT_FIRST_PASS) HIP_TRY(hipEventSynchronize(h->ev_first));
+    else HIP_TRY(hipStreamSynchronize(h->stream));      /* (the copy of the final stats records is the last thing the batch enqueued) */
+    int pending = 0;
+    for (int k = 0; k < h->begun; k++) pending += h->h_done[k] == 0;
+    if (n_pending) *n_pending = pending;
+    if (what == MSD_WAIT_ALL) h->begun = 0;
+    return MSD_OK;
+}
+
+int msd_solve_batch_done(msd_handle h, const volatile int **words, const double **stats_now)
+{
+    if (!h || !words || !stats_now) return fail(MSD_E_INVALID, "bad argument");
+    if (!h->h_done) return fail(MSD_E_INVALID, "no batch has been begun on this handle (msd_solve_batch_begin)");
+    *words = h->h_done; *stats_now = h->h_stats_now;
+    return MSD_OK;
 }
 
 int msd_problem_direct_results(msd_handle h, int on)
@@ -792,6 +874,7 @@ int msd_solve_batch_multi(const msd_handle *handles, int nhandles, int nscen, co
             return fail(MSD_E_INVALID, "the handles of a multi-device solve must hold the same problem");
         for (int j = 0; j < k; j++)
             if (handles[j] == handles[k]) return fail(MSD_E_INVALID, "a handle appears twice");
+        if (handles[k]->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
     }
     int rc = check_batch(handles[0], nscen, scen, overrides, z_guess, mu_init, bound_push, z_out, stats);
     if (rc != MSD_OK) return rc;

@@ -63,7 +63,9 @@ struct WarmStart { const double *d_guess = nullptr; long long stride = 0; const 
                    const double *d_dual_in = nullptr; long long dual_stride = 0; int dual_shift = 0; double *d_dual_out = nullptr;
                    bool one_attempt = false;         /* a solve that breaks down is not repeated from the other starting point (msd_mpc.hip: the loop certifies it first) */
                    bool use_soc = false;             /* the first-pass kernel with the second-order correction inside (Plan::kernel_soc), where the plan has one */
-                   int *d_soc_seen = nullptr; };     /* DevProb::socSeen of the launch (device address of a mapped host word) */
+                   int *d_soc_seen = nullptr;        /* DevProb::socSeen of the launch (device address of a mapped host word) */
+                   int *d_done = nullptr; double *d_stats_host = nullptr;      /* DevProb::done, statsHost: early results (msd_solve_batch_begin) */
+                   int budget = 0; };                /* DevProb::budget (msd_problem_iteration_budget) */
 
 /*
  * One batch on `stream`: the first pass + the follow-up kernel of a split solve, or the one kernel that holds everything.
@@ -117,6 +119,15 @@ struct msd_problem {
     bool time_first_pass = false;
     hipEvent_t fp_beg[FP_RING] = {}, fp_end[FP_RING] = {};
     long long fp_count = 0;
+    /* early results (msd_problem_early_results): completion words and the mirror of the stats records, mapped host memory that grows with the largest
+     * batch; msd_solve_batch_begin ... msd_solve_batch_wait(MSD_WAIT_ALL) */
+    bool early_results = false;
+    int budget = 0;                                     /* msd_problem_iteration_budget */
+    volatile int *h_done = nullptr; int *d_done = nullptr;
+    double *h_stats_now = nullptr, *d_stats_now = nullptr;
+    int cap_done = 0;
+    int begun = 0;                                      /* scenarios of the batch begun and not yet waited for in full (0: none) */
+    hipEvent_t ev_first = nullptr;                      /* behind the first kernel of the begun batch */
     int attached_loops = 0;                             /* receding-horizon loops (msd_mpc_create) that run on this handle's stream: it cannot be destroyed while one exists */
 };
 

@@ -112,10 +112,18 @@ struct DevProb {
                               * `follow`; a first-pass kernel can be given a list too -- msd_mpc.hip's re-solves -- and hands over through `follow` as usual) */
     int *socSeen;            /* not null: a word of host memory mapped into the device; a first-pass kernel that hands a scenario over for a second-order correction sets it,
                               * and the handle's next launches take the first-pass kernel that has the correction inside its fused iteration (msd_api.hip: launch) */
+    /* early results (msd_solve_batch_begin): a caller reads the scenarios that have ended while the others still run */
+    int *done;               /* not null: completion words in mapped host memory, one per scenario, zeroed by the launch code.  The kernel that ends a scenario stores
+                              * 1 (a first pass) or 2 (a follow-up kernel) there, with release ordering at system scope, behind everything it stored for that scenario;
+                              * a scenario that is handed over keeps its 0 until the follow-up kernel has ended it */
+    double *statsHost;       /* not null (with done): mapped host mirror of the stats records, a scenario's record written in front of its word */
+    int budget;              /* > 0: iterations a first pass spends on a scenario before it hands it over (reason 7) to the follow-up kernel, which solves it from its
+                              * starting point under the problem's own iteration limit; 0: none */
 };
 /* behind the three counters: telemetry that is never reset -- [3] scenarios listed so far, [4 + why] by reason: 0 no fused start for the scenario
  * (a warm start whose previous solve failed), 1 wrong inertia or a scan breakdown, 2 tiny step, 3 first trial point rejected where a
- * second-order correction applies, 4 line search broke down (restoration phase), 5 a breakdown that asks for the second attempt */
+ * second-order correction applies, 4 line search broke down (restoration phase), 5 a breakdown that asks for the second attempt (counted, solved
+ * by the first pass itself), 7 the first pass's iteration budget ran out (DevProb::budget) */
 constexpr int FOLLOW_HDR = 16, FOLLOW_TOTAL = 3, FOLLOW_WHY = 4;
 
 /* IPOPT default option values */
@@ -162,7 +170,7 @@ constexpr int RED_K = 8, RED_SLOTS = 4, MAX_WAVES = 16;
 constexpr int MISC_FALLBACKS = 24;  /* misc[24]: KKT solves of this scenario that fell back from the scan to the serial sweep */
 constexpr int MISC_LG = 16;        /* misc[16..22]: last interval's Fel row for the multiplier of its eliminated b row */
 constexpr int HIST_COLS = 8;
-constexpr int CONST_DOUBLES = 96, UNI_OFF = 48;    /* LDS copies of the problem record (DevProb) and of the scenario's uniform data (Uni), behind misc */
+constexpr int CONST_DOUBLES = 96, UNI_OFF = 52;    /* LDS copies of the problem record (DevProb) and of the scenario's uniform data (Uni), behind misc */
 
 /* stage block slots.  Written by the owning thread in assemble(): the dynamics (0..5, never overwritten), the condensed
  * Hessian/gradient of (t, b, q | f, p) with the slack variable s already eliminated (6..22), and what the elimination needs
@@ -751,6 +759,17 @@ __device__ __forceinline__ void opaque(double &v) { asm volatile("" : "+v"(v)); 
 __device__ __forceinline__ void opaque_a(double &v) { asm volatile("" : "+a"(v)); }
 __device__ __forceinline__ void opaque_z(double &v) { if (MSD_FENCE_AGPR >= 1) opaque_a(v); else opaque(v); }
 __device__ __forceinline__ void opaque_d(double &v) { if (MSD_FENCE_AGPR >= 2) opaque_a(v); else opaque(v); }
+
+/* a scenario's completion word (DevProb::done): everything the workgroup stored for the scenario in front of the barrier that precedes this call is
+ * visible to a host thread that reads the word as set */
+__device__ __forceinline__ void publish_done(int *word, int v)
+{
+#ifdef MSD_HOST_EMULATION
+    __atomic_store_n(word, v, __ATOMIC_RELEASE);
+#else
+    __hip_atomic_store(word, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+#endif
+}
 
 /* a workgroup-uniform value into scalar registers */
 __device__ __forceinline__ int wg_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -4431,6 +4450,10 @@ __global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, co
             Ps.fmax = o[MSD_OV_F_MAX]; Ps.fmin = o[MSD_OV_F_MIN]; Ps.fminPn = o[MSD_OV_F_MIN_PN];
             Ps.pwU = o[MSD_OV_PW_UPPER]; Ps.pwL = o[MSD_OV_PW_LOWER]; Ps.objDen = o[MSD_OV_OBJ_DEN]; Ps.lossMass = o[MSD_OV_TOTAL_MASS];
         }
+        /* iteration budget of a first pass that can hand over: its iteration limit; a scenario that runs into it is the follow-up kernel's (below) */
+        const bool budgeted = SolverT::FIRST && P.follow && P.budget > 0 && P.budget < P.maxIter;
+        if (budgeted) Ps.maxIter = P.budget;
+        bool handed = false;      /* the scenario does not end in this kernel (uniform: decided on the uniform status) */
         __syncthreads();
         if (c.tid == 0) *Pl = Ps;
         __syncthreads();
@@ -4483,16 +4506,18 @@ __global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, co
                 /* done (solved, or out of iterations: no second attempt for that) -- or the follow-up kernel's: the general iteration from the same
                  * starting point (also a line search that broke down where the follow-up kernel has the restoration phase).  A breakdown is
                  * repeated here, from the other starting point, like in the kernels that hold everything */
-                if (st >= 0 || st == MSD_STATUS_INFEASIBLE || st == MSD_STATUS_MAXITER) break;
-                const bool again = st == SolverT::STATUS_GENERAL || (SolverT::FAMILY_HAS_RESTO && st == MSD_STATUS_LINESEARCH && P.resto);
+                const bool over_budget = budgeted && st == MSD_STATUS_MAXITER;      /* (handed over as a first attempt, whichever attempt ran out) */
+                if (st >= 0 || st == MSD_STATUS_INFEASIBLE || (st == MSD_STATUS_MAXITER && !over_budget)) break;
+                const bool again = st == SolverT::STATUS_GENERAL || (SolverT::FAMILY_HAS_RESTO && st == MSD_STATUS_LINESEARCH && P.resto) || over_budget;
                 if (again) {
                     if (c.tid == 0) {
                         const int k = atomicAdd(P.follow, 1);
-                        P.follow[FOLLOW_HDR + 2*k] = sidx; P.follow[FOLLOW_HDR + 2*k + 1] = attempt == 0 ? -1 : spent;
+                        P.follow[FOLLOW_HDR + 2*k] = sidx; P.follow[FOLLOW_HDR + 2*k + 1] = (attempt == 0 || over_budget) ? -1 : spent;
                         atomicAdd(P.follow + FOLLOW_TOTAL, 1);
-                        atomicAdd(P.follow + FOLLOW_WHY + (st == SolverT::STATUS_GENERAL ? s.why_general : 4), 1);
+                        atomicAdd(P.follow + FOLLOW_WHY + (over_budget ? 7 : st == SolverT::STATUS_GENERAL ? s.why_general : 4), 1);
                         if (P.socSeen && st == SolverT::STATUS_GENERAL && s.why_general == 3) *P.socSeen = 1;
                     }
+                    handed = true;
                     break;
                 }
                 if (P.oneAttempt) break;
@@ -4532,6 +4557,14 @@ __global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, co
             if (guess) guess = nullptr;      /* a warm start that breaks down: once more from the problem's own starting point */
             else startKind = (startKind == MSD_START_PROFILE) ? MSD_START_REFERENCE : MSD_START_PROFILE;
             }
+        }
+        if (P.done) {
+            /* early results: the scenario has ended here -- z*, the multipliers and the stats record are stored (a barrier follows every run()); the record's
+             * mirror, the barrier that puts every wave's stores in front of the word, the word.  The branch is on a kernel argument: uniform */
+            const int word = handed ? 0 : (PART == 2 ? 2 : 1);
+            if (word != 0 && P.statsHost && c.tid < MSD_ST_COUNT) P.statsHost[(size_t)MSD_ST_COUNT*sidx + c.tid] = stats[(size_t)MSD_ST_COUNT*sidx + c.tid];
+            __syncthreads();
+            if (word != 0 && c.tid == 0) publish_done(P.done + sidx, word);
         }
     }
     if (listed) {

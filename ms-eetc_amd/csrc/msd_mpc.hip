@@ -297,6 +297,7 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
     if (!(initial_time >= 0)) return fail(MSD_E_INVALID, "Initial time must be a positive number!");
     for (int s = 0; s < nscen; s++) if (!(T[s] > 0)) return fail(MSD_E_INVALID, "Terminal time must be a strictly positive number!");
     msd_problem *h = m->h;
+    if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
     HIP_TRY(hipSetDevice(h->device));
     const int B = nscen, K = m->K;
     int rc = grow(m, B, z_log != nullptr);

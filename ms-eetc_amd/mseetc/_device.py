@@ -24,6 +24,7 @@ OV = dict(SR0=0, SR1=1, SR2=2, F_MAX=3, F_MIN=4, F_MIN_PN=5, PW_UPPER=6, PW_LOWE
 HIST_COLS = 8
 
 STATUS_MAXITER, STATUS_LINESEARCH, STATUS_INFEASIBLE = -1, -2, -6
+WAIT_FIRST_PASS, WAIT_ALL = 1, 2      # MSD_WAIT_*
 # -2: the filter line search broke down and the feasibility restoration phase (csrc/msd_resto.hpp, IPOPT's MinC_1Nrm restoration) did not
 # find an acceptable point either -- IPOPT's 'Restoration_Failed'.  -6: the restoration phase converged to a stationary point of the
 # infeasibility (device), or the minimum-running-time certificate of a failed scenario says so (casadiSolver._classify_failures).
@@ -101,6 +102,11 @@ def lib():
                                               ctypes.POINTER(ctypes.c_float)]
         L.msd_problem_keep_duals.argtypes = [vp, ctypes.c_int]
         L.msd_problem_direct_results.argtypes = [vp, ctypes.c_int]
+        L.msd_problem_early_results.argtypes = [vp, ctypes.c_int]
+        L.msd_problem_iteration_budget.argtypes = [vp, ctypes.c_int]
+        L.msd_solve_batch_begin.argtypes = [vp, ctypes.c_int, _dptr, _dptr, _dptr, _dptr, _dptr]
+        L.msd_solve_batch_wait.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.msd_solve_batch_done.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(ctypes.c_int)), ctypes.POINTER(_dptr)]
         L.msd_solve_batch_multi.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, _dptr, _dptr, _dptr, ctypes.c_double, ctypes.c_double, _dptr, _dptr,
                                             _dptr, ctypes.POINTER(ctypes.c_float)]
         L.msd_solve_batch_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp]
@@ -247,6 +253,59 @@ class _ResultArrays():
         return np.frombuffer(carr, dtype=np.float64, count=count).reshape(shape)      # (every element is written by the copy that follows)
 
 
+class PendingBatch():
+    """
+    A batch begun with DeviceProblem.solve_batch_begin: both kernels are enqueued, nothing has been waited for.  `done` is an int32 view of the
+    completion words in host memory the kernels write (0 not ended, 1 ended by the first pass, 2 ended by the follow-up kernel): once a
+    scenario's word is non-zero its rows of z, lam_g and of the stats mirror are final.  No HIP call is needed to read it.
+    """
+
+    def __init__(self, problem, B, z, lam, st):
+
+        self._problem, self._B, self._z, self._lam, self._st, self._finished = problem, B, z, lam, st, False
+        words, stats_now = ctypes.POINTER(ctypes.c_int)(), _dptr()
+        _check(lib().msd_solve_batch_done(problem._h, ctypes.byref(words), ctypes.byref(stats_now)))
+        # (views of the handle's own buffers: they stay where they are until a larger batch is begun on the handle)
+        self.done = np.ctypeslib.as_array(words, shape=(B,))
+        self._stats_now = np.ctypeslib.as_array(stats_now, shape=(B, ST['COUNT']))
+
+    def _wait(self, what):
+        n = ctypes.c_int(0)
+        _check(lib().msd_solve_batch_wait(self._problem._h, what, ctypes.byref(n)))
+        return n.value
+
+    def wait_first_pass(self):
+        "Wait for the first of the two kernels; the boolean mask of the scenarios that have ended (more may end while the caller looks)."
+
+        if not self._finished:
+            self._wait(WAIT_FIRST_PASS)
+        return self.done != 0
+
+    def snapshot(self):
+        "The dict of solve_batch as it stands now -- copies; a scenario's rows are valid where its completion word was non-zero before the call."
+
+        mask = self.done != 0      # (read in front of the rows: a word that reads non-zero has its rows behind it)
+        out = dict(z=self._z.copy(), stats=self._stats_now.copy(), lam_g=self._lam.copy() if self._lam is not None else None, kernel_ms=0.0)
+        out['done'] = mask
+        return out
+
+    def result(self):
+        "Wait for everything: the dict of solve_batch."
+
+        if not self._finished:
+            self._wait(WAIT_ALL)
+            self._finished = True
+        return dict(z=self._z, stats=self._st, lam_g=self._lam, kernel_ms=0.0)
+
+    def __del__(self):
+        # (a batch nobody took the result of: its kernels still write the result arrays this object keeps alive)
+        try:
+            if not self._finished and getattr(self._problem, '_h', None):
+                self.result()
+        except Exception:
+            pass
+
+
 class DeviceProblem():
     "Owner of an msd_handle."
 
@@ -335,6 +394,43 @@ class DeviceProblem():
 
         return out
 
+    def iteration_budget(self, k):
+        """
+        Iterations the first pass spends on a scenario before it hands it to the follow-up kernel, which solves it from its starting point under
+        the problem's own iteration limit (msd_problem_iteration_budget); 0: none.
+        """
+
+        _check(lib().msd_problem_iteration_budget(self._h, int(k)))
+        return self
+
+    def early_results(self, on=True):
+        "Completion words per scenario for solve_batch_begin (msd_problem_early_results)."
+
+        _check(lib().msd_problem_early_results(self._h, int(bool(on))))
+        return self
+
+    def solve_batch_begin(self, scen, want_multipliers=False, overrides=None):
+        """
+        solve_batch without the wait (msd_solve_batch_begin): returns a PendingBatch whose finished scenarios can be read while the stragglers
+        still run.  Until its result() has been taken the handle accepts no other solve.
+        """
+
+        L = lib()
+        scen = np.ascontiguousarray(scen, dtype=np.float64).reshape(-1, SC_COUNT)
+        B = scen.shape[0]
+        self.early_results(True)
+        z = self._results.empty('z', (B, self.nz))
+        st = self._results.empty('st', (B, ST['COUNT']))
+        lam = self._results.empty('lam', (B, self.rowsPerInterval*self.N)) if want_multipliers else None
+
+        if overrides is not None:
+            overrides = np.ascontiguousarray(overrides, dtype=np.float64).reshape(B, OV['COUNT'])
+
+        _check(L.msd_solve_batch_begin(self._h, B, _d(scen), _d(overrides) if overrides is not None else None, _d(z),
+                                       _d(lam) if lam is not None else None, _d(st)))
+
+        return PendingBatch(self, B, z, lam, st)
+
     def solve_batch_multi(self, others, scen, want_multipliers=False, overrides=None, guess=None, warmMu=1e-2, warmPush=1e-3):
         """
         solve_batch over this handle and `others` (DeviceProblems of the same problem, normally on other devices): contiguous
@@ -416,9 +512,9 @@ class DeviceProblem():
         return float(ms.value), int(n.value)
 
     def follow_counts(self):
-        "Scenarios the first-pass kernel handed to the follow-up kernel so far: (total, by reason[7]) -- msd_problem_follow_counts."
-        out = (ctypes.c_int*8)()
-        _check(lib().msd_problem_follow_counts(self._h, out, 8))
+        "Scenarios the first-pass kernel handed to the follow-up kernel so far: (total, by reason[8]) -- msd_problem_follow_counts."
+        out = (ctypes.c_int*9)()
+        _check(lib().msd_problem_follow_counts(self._h, out, 9))
         return int(out[0]), [int(v) for v in out[1:]]
 
     def timer_begin(self):

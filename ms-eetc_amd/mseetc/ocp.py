@@ -300,7 +300,8 @@ class casadiSolver():
         return out
 
     def solveBatch(self, terminalTime, initialTime=0, terminalVelocity=1, initialVelocity=1, multipliers=False,
-                   mass=None, r0=None, r1=None, r2=None, guess=None, warmMu=1e-2, warmPush=1e-3, devices=None, classifyFailures=True, shift=None):
+                   mass=None, r0=None, r1=None, r2=None, guess=None, warmMu=1e-2, warmPush=1e-3, devices=None, classifyFailures=True, shift=None,
+                   onFirstPass=None):
         """
         Solve many scenarios of this problem in one launch.  Arguments broadcast against each other; `mass`, `r0`, `r1`, `r2`
         (SI units, scalars or one value per scenario) perturb the rolling stock per scenario.  `guess` (B, nz) or (nz,), in the
@@ -308,6 +309,10 @@ class casadiSolver():
         cold-starts like the reference (ocp.py:325-339).
         Returns dict: 'z' (B, nz) in the reference's variable layout, 'status' (B,), 'iterations' (B,), 'cost' (B,)
         [kWh or s], 'stats' (raw records), 'kernel_ms', optionally 'lam_g'.
+        `onFirstPass`: callable(mask, partialResult), called once when the first of the launch's two kernels has ended, while the follow-up
+        kernel may still work on the stragglers: `mask` (B,) marks the scenarios that have ended, `partialResult` holds 'z', 'status',
+        'iterations', 'cost', 'stats' and 'lam_g', valid where the mask is true (failures there are not classified yet).  The return value is the same
+        as without it.  Not combined with `guess`, `shift` or `devices`.
         """
 
         scen = self._scenarios(terminalTime, initialTime, terminalVelocity, initialVelocity)
@@ -325,7 +330,21 @@ class casadiSolver():
                 raise ValueError("Warm-start guess must be finite!")
             guess = np.broadcast_to(guess.reshape(-1, nz), (B, nz))
 
-        if devices is None:
+        if onFirstPass is not None:
+            if guess is not None or shift is not None or devices is not None:
+                raise ValueError("onFirstPass is not combined with guess, shift or devices!")
+            pending = self.problem.solve_batch_begin(scen, want_multipliers=multipliers, overrides=self._overrides(B, mass, r0, r1, r2))
+            try:
+                pending.wait_first_pass()
+                part = pending.snapshot()
+                mask = part['done']      # (the snapshot reads the words in front of its copies: the follow-up kernel may have ended some by now)
+                pst = part['stats']
+                onFirstPass(mask, dict(z=part['z'], status=pst[:, _device.ST['STATUS']].astype(int), iterations=pst[:, _device.ST['ITERS']].astype(int),
+                                       cost=pst[:, _device.ST['OBJ']]*(1.0 if self.energyOptimal else self.scalingFactorObjective), stats=pst,
+                                       lam_g=part['lam_g']))
+            finally:
+                out = pending.result()      # (the handle takes no other solve before the batch has been waited for)
+        elif devices is None:
             out = self.problem.solve_batch(scen, want_multipliers=multipliers, overrides=self._overrides(B, mass, r0, r1, r2),
                                            guess=guess, warmMu=warmMu, warmPush=warmPush, shift=shift)
         else:
