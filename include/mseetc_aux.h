@@ -40,7 +40,9 @@ int msd_problem_direct_results(msd_handle h, int on);
 /*
  * Tuning switches of the kernel pickers for the problems created afterwards (process-wide; A/B measurements and one GPU test -- the library itself reads no
  * environment variable).  "no_full" != 0: the kernels without the structure of the NLP compiled in; "two_nodes_per_lane" != 0: the 64 x 2 geometry for
- * horizons of 64 ... 127 intervals of the shooting-integrator and integrateLosses families (default 128 x 1).  Unknown name: MSD_E_INVALID.
+ * horizons of 64 ... 127 intervals of the shooting-integrator and integrateLosses families (default 128 x 1); "geometry" = 16 NT + SPT: every rung of the
+ * ladder offers NT threads with SPT nodes each instead of its own geometry, whatever the horizon (0: off; a GPU test runs short horizons on the 64 x 2
+ * kernels with it).  Unknown name: MSD_E_INVALID.
  */
 int msd_tuning(const char *name, int value);
 
@@ -51,6 +53,13 @@ int msd_tuning(const char *name, int value);
  * description msd_problem_create would reject gets the same code and msd_last_error() here (tests/test_abi.py pins the table).
  */
 int msd_plan_describe(const msd_problem_desc *desc, char *buf, int len);
+
+/*
+ * The symbol name of the first kernel of the handle's last launch, in buf (len bytes; "-": the handle has launched nothing yet): the first pass of a split
+ * solve, or the one kernel of the others.  The first passes of the fused family exist twice -- the default kernels, and twins with the early results inside
+ * that a begun batch (msd_solve_batch_begin) or an iteration budget (msd_problem_iteration_budget) launches; the tests see here which one ran.
+ */
+int msd_problem_last_first_pass(msd_handle h, char *buf, int len);
 
 /*
  * Test hook: the reciprocal and the square root / reciprocal square root of the fused interior-point iteration (csrc/msd_fastmath.hpp: v_rcp_f64 /

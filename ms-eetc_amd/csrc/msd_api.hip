@@ -27,7 +27,7 @@ thread_local std::string g_err;
 }
 
 /* the lookups of the kernel units (msd_kernels_<unit>.hip: kernels_<unit>) */
-#define MSD_KERNEL_UNITS(X) X(full) X(full2) X(full3) X(full4) X(rg) X(rg2) X(static) X(time) X(time2) X(dynamic) X(dynamic2) X(dynamic3) X(stream) X(stream2) X(stream3) \
+#define MSD_KERNEL_UNITS(X) X(full) X(full2) X(full3) X(full4) X(full5) X(full6) X(rg) X(rg2) X(rg3) X(static) X(time) X(time2) X(dynamic) X(dynamic2) X(dynamic3) X(stream) X(stream2) X(stream3) \
     X(stream4) X(stream5) X(stream6) X(stream7) X(compose) X(general) X(general2) X(intloss) X(intloss_table) X(intloss_table2)
 namespace msd {
 #define X(unit) KernelFn kernels_##unit(const KernelId &id);
@@ -164,6 +164,8 @@ int select_plan(const msd_problem_desc *d, Plan *out, msd::KernelFn *soc_out)
     pl.kernel = find_kernel(geo.first); pl.kernel2 = find_kernel(geo.follow); pl.kernel_lsq = find_kernel(geo.lsq);      /* (the ladder hands out only ids the build holds) */
     pl.kernel_soc = nullptr;
     *soc_out = find_kernel(geo.soc);
+    /* the twins with the early results inside (candidates: make_plan asks the device) */
+    pl.kernel_early = find_kernel(geo.early(geo.first)); pl.kernel_lsq_early = find_kernel(geo.early(geo.lsq)); pl.kernel_soc_early = find_kernel(geo.early(geo.soc));
     return MSD_OK;
 }
 
@@ -197,6 +199,14 @@ int make_plan(int device, const msd_problem_desc *d, Plan *out)
         int per_cu_soc = 0;
         if (kernel_limits(device, (const void *)soc, pl.NT, pl.lds_bytes, &per_cu_soc) == MSD_OK && per_cu_soc*cus >= pl.max_grid) pl.kernel_soc = soc;
     }
+    /* the twins with the early results inside run in their default kernel's launch: taken when as resident (same registers but for a handful of scalars,
+     * same LDS).  A launch that needs a twin the plan does not have fails (launch_plan) */
+    const auto twin = [&](msd::KernelFn &early, msd::KernelFn plain, int grid) {
+        int per_cu_early = 0;
+        if (!plain) early = nullptr;
+        else if (early && early != plain && !(kernel_limits(device, (const void *)early, pl.NT, pl.lds_bytes, &per_cu_early) == MSD_OK && per_cu_early*cus >= grid)) early = nullptr;
+    };
+    twin(pl.kernel_early, pl.kernel, pl.max_grid); twin(pl.kernel_lsq_early, pl.kernel_lsq, pl.max_grid_lsq); twin(pl.kernel_soc_early, pl.kernel_soc, pl.max_grid);
     return MSD_OK;
 }
 
@@ -234,7 +244,8 @@ std::string plan_text(const Plan &pl, msd::KernelFn soc)
 }
 
 int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follow, int *d_queue, int nscen, const double *d_scen, const double *d_ovr,
-                double *d_z, double *d_lam, double *d_stats, double *d_hist, int hist_cap, const WarmStart &ws, int *d_list, hipEvent_t first_begin, hipEvent_t first_end)
+                double *d_z, double *d_lam, double *d_stats, double *d_hist, int hist_cap, const WarmStart &ws, int *d_list, hipEvent_t first_begin, hipEvent_t first_end,
+                msd::KernelFn *first_out)
 {
     if (!pl.kernel) return fail(MSD_E_INVALID, "the handle holds no problem: its last (re)configuration failed");
     msd::DevProb P = pl.P;
@@ -252,6 +263,7 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
         const msd::KernelFn fn = split ? pl.kernel2 : pl.kernel;
         const int cap = split ? pl.max_grid2 : pl.max_grid;
         P.list = d_list;
+        if (first_out) *first_out = fn;
         hipLaunchKernelGGL(fn, dim3(std::min(nscen, cap)), dim3(split ? pl.NT2 : pl.NT), split ? pl.lds_bytes2 : pl.lds_bytes, stream, P, nscen, d_scen, d_ovr, d_z, d_lam, d_stats, d_hist, hist_cap, d_work);
         HIP_TRY(hipGetLastError());
         return MSD_OK;
@@ -260,7 +272,13 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
     /* split solves (msd::Geometry::follow): first pass + follow-up kernel behind it on the stream, the list of unfinished scenarios between them.
      * The first pass is the kernel without the least-squares multiplier estimate when every scenario can start without it (profile start,
      * primal-dual warm start), the one with it otherwise (the reference's starting point, a primal-only warm start) */
-    const msd::KernelFn fn = (split && !first_pass) ? pl.kernel2 : plain ? ((ws.use_soc && pl.kernel_soc) ? pl.kernel_soc : pl.kernel) : pl.kernel_lsq;
+    /* ... and its twin with the early results inside for a begun batch or an iteration budget (the same mechanism as kernel_soc; a follow-up kernel is its own) */
+    const bool early = ws.d_done != nullptr || ws.budget > 0;
+    const msd::KernelFn fn = (split && !first_pass) ? pl.kernel2
+                           : plain ? ((ws.use_soc && pl.kernel_soc && (!early || pl.kernel_soc_early)) ? (early ? pl.kernel_soc_early : pl.kernel_soc) : (early ? pl.kernel_early : pl.kernel))
+                                   : (early ? pl.kernel_lsq_early : pl.kernel_lsq);
+    if (!fn) return fail(MSD_E_UNSUPPORTED, "this build holds no first-pass kernel with the early results inside for the handle's problem");
+    if (first_out) *first_out = fn;
     const int cap = (split && !first_pass) ? pl.max_grid2 : plain ? pl.max_grid : pl.max_grid_lsq;
     const int grid = nscen < cap ? nscen : cap;
     const int threads = (split && !first_pass) ? pl.NT2 : pl.NT;
@@ -308,6 +326,7 @@ int msd_tuning(const char *name, int value)
     if (!name) return fail(MSD_E_INVALID, "null argument");
     if (!strcmp(name, "no_full")) msd_host::tuning().no_full = value != 0;
     else if (!strcmp(name, "two_nodes_per_lane")) msd_host::tuning().two_nodes_per_lane = value != 0;
+    else if (!strcmp(name, "geometry")) { msd_host::tuning().NT = value > 0 ? value/16 : 0; msd_host::tuning().SPT = value > 0 ? value%16 : 0; }
     else return fail(MSD_E_INVALID, std::string("unknown tuning switch: ") + name);
     return MSD_OK;
 }
@@ -517,7 +536,16 @@ static int launch(msd_handle h, int nscen, const double *d_scen, const double *d
                 nscen, (void *)h->d_work, sizeof(double)*h->cap_work, (void *)h->d_follow, (void *)queue, (void *)h->d_prof, (const void *)d_scen, (void *)d_z, (void *)d_lam, (void *)d_stats, (void *)d_hist,
                 msd_host::plan_text(h->plan, h->plan.kernel_soc).c_str(), h->plan.max_grid, h->plan.max_grid_lsq, h->plan.max_grid2);
 #endif
-    return msd_host::launch_plan(h->plan, h->stream, h->d_work, h->d_follow, queue, nscen, d_scen, d_ovr, d_z, d_lam, d_stats, d_hist, hist_cap, ws, nullptr, e0, e1);
+    return msd_host::launch_plan(h->plan, h->stream, h->d_work, h->d_follow, queue, nscen, d_scen, d_ovr, d_z, d_lam, d_stats, d_hist, hist_cap, ws, nullptr, e0, e1, &h->last_first);
+}
+
+int msd_problem_last_first_pass(msd_handle h, char *buf, int len)
+{
+    if (!h || !buf || len < 1) return fail(MSD_E_INVALID, "null argument");
+    const std::string name = msd_host::kernel_name(h->last_first);
+    if ((int)name.size() >= len) return fail(MSD_E_INVALID, "msd_problem_last_first_pass: the name needs " + std::to_string(name.size() + 1) + " bytes");
+    memcpy(buf, name.c_str(), name.size() + 1);
+    return MSD_OK;
 }
 
 int msd_solve_batch_device(msd_handle h, int nscen, const double *d_scen, double *d_z, double *d_lam, double *d_stats)

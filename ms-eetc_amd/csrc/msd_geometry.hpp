@@ -16,17 +16,19 @@ struct KernelId {
     int NT = 0, SPT = 0, WPS = 1, DYN = LOSS_STATIC;
     bool STREAM = false, GEN = false;
     int FULL = 0, PART = 0;
-    bool SLDS = false, SOCK = false;
+    bool SLDS = false, SOCK = false, EARLY = false;
     explicit operator bool() const { return NT != 0; }
 };
 inline bool operator==(const KernelId &a, const KernelId &b)
 {
     return a.NT == b.NT && a.SPT == b.SPT && a.WPS == b.WPS && a.DYN == b.DYN && a.STREAM == b.STREAM && a.GEN == b.GEN && a.FULL == b.FULL && a.PART == b.PART
-           && a.SLDS == b.SLDS && a.SOCK == b.SOCK;
+           && a.SLDS == b.SLDS && a.SOCK == b.SOCK && a.EARLY == b.EARLY;
 }
 
 /* one entry of a unit's lookup `KernelFn kernels_<unit>(const KernelId &id)`: the instantiation with these template arguments lives in this unit */
 #define MSD_KERNEL(...) if (id == KernelId{__VA_ARGS__}) return solve_kernel<__VA_ARGS__>;
+/* ... its twin with the early results inside (solve_kernel_early: the id with EARLY set) */
+#define MSD_KERNEL_EARLY(...) if (KernelId twin_{__VA_ARGS__}; (twin_.EARLY = true, id == twin_)) return solve_kernel_early<__VA_ARGS__>;
 /* ... and an instantiation the unit compiles that no rung of the ladder picks (it was instantiated when the ladder was a template over the loss model): kept, so that
  * the unit's code object stays what it was; the host side drops it */
 #define MSD_KERNEL_UNUSED(...) if (false) return solve_kernel<__VA_ARGS__>;
@@ -37,6 +39,9 @@ struct Geometry {
     KernelId follow;                     /* the follow-up kernel of a split solve (PART = 2), with its own NT and SPT: it restarts a scenario from its starting point, so nothing ties its geometry to the first pass's */
     KernelId lsq;                        /* first pass with the least-squares multiplier estimate in front (PART = 3): launches from the reference's starting point or a primal-only warm start */
     KernelId soc;                        /* `first` with the second-order correction inside the fused iteration (SOCK: msd_kernels_full4.hip), same launch */
+    /* the twins of first / lsq / soc that hold the early results (solve_kernel: EARLY), same launch: the fused family's first passes have them;
+     * everywhere else the kernel itself tests for them at run time and is its own twin */
+    KernelId early(const KernelId &k) const { KernelId e = k; if (k && xch == XCH_FAST && (k.PART == 1 || k.PART == 3)) e.EARLY = true; return e; }
     bool stream = false;                 /* stage blocks in device memory (long horizons) */
     int xch = XCH_GENERAL;               /* exchange arrays in LDS and cross-wave reduction scratch (lds_doubles) */
     int red = RED_DOUBLES;

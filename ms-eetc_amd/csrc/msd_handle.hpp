@@ -35,6 +35,9 @@ struct Plan {
     msd::KernelFn kernel_lsq = nullptr;               /* first pass for launches that need the least-squares multiplier estimate (msd::Geometry::lsq) */
     msd::KernelFn kernel2 = nullptr;                  /* follow-up kernel of a split solve (msd::Geometry::follow) */
     msd::KernelFn kernel_soc = nullptr;               /* `kernel` with the second-order correction inside the fused iteration (msd::Geometry::soc): WarmStart::use_soc */
+    /* kernel, kernel_lsq and kernel_soc with the early results inside (msd::Geometry::early): what a launch with completion words or an iteration budget
+     * takes.  The first passes of the fused family have such twins (taken when as resident as the default kernel); every other kernel is its own twin */
+    msd::KernelFn kernel_early = nullptr, kernel_lsq_early = nullptr, kernel_soc_early = nullptr;
     int NT2 = 0, SPT2 = 0;                            /* its own launch geometry (it restarts a scenario from its starting point, so it need not share the first pass's) */
     size_t lds_bytes2 = 0;
     int max_grid = 0, max_grid_lsq = 0, max_grid2 = 0;      /* resident workgroups of the three */
@@ -77,7 +80,8 @@ struct WarmStart { const double *d_guess = nullptr; long long stride = 0; const 
  */
 int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follow, int *d_queue, int nscen, const double *d_scen, const double *d_ovr,
                 double *d_z, double *d_lam, double *d_stats, double *d_hist, int hist_cap, const WarmStart &ws, int *d_list = nullptr,
-                hipEvent_t first_begin = nullptr, hipEvent_t first_end = nullptr);      /* (events recorded around the first kernel of the launch) */
+                hipEvent_t first_begin = nullptr, hipEvent_t first_end = nullptr,      /* (events recorded around the first kernel of the launch) */
+                msd::KernelFn *first_out = nullptr);                                     /* (not null: receives the first kernel of the launch) */
 
 }  // namespace msd_host
 
@@ -128,6 +132,7 @@ struct msd_problem {
     int cap_done = 0;
     int begun = 0;                                      /* scenarios of the batch begun and not yet waited for in full (0: none) */
     hipEvent_t ev_first = nullptr;                      /* behind the first kernel of the begun batch */
+    msd::KernelFn last_first = nullptr;                 /* the first kernel of the handle's last launch (msd_problem_last_first_pass) */
     int attached_loops = 0;                             /* receding-horizon loops (msd_mpc_create) that run on this handle's stream: it cannot be destroyed while one exists */
 };
 

@@ -121,7 +121,8 @@ struct DevProb {
                               * starting point under the problem's own iteration limit; 0: none */
 };
 /* behind the three counters: telemetry that is never reset -- [3] scenarios listed so far, [4 + why] by reason: 0 no fused start for the scenario
- * (a warm start whose previous solve failed), 1 wrong inertia or a scan breakdown, 2 tiny step, 3 first trial point rejected where a
+ * (a warm start whose previous solve failed; a scenario or an override that fixes a variable the compiled-in structure has free -- t0 == tEnd, f_min == f_max,
+ * f_min_pn == 0, an interior speed limit equal to the minimum speed: Solver::structural_start), 1 wrong inertia or a scan breakdown, 2 tiny step, 3 first trial point rejected where a
  * second-order correction applies, 4 line search broke down (restoration phase), 5 a breakdown that asks for the second attempt (counted, solved
  * by the first pass itself), 7 the first pass's iteration budget ran out (DevProb::budget) */
 constexpr int FOLLOW_HDR = 16, FOLLOW_TOTAL = 3, FOLLOW_WHY = 4;
@@ -663,6 +664,11 @@ __device__ __forceinline__ bool cmp_le(double lhs, double rhs, double basval) { 
  * Bounds are not stored per variable: only the upper bound of b is node dependent.
  * ---------------------------------------------------------------------------------------- */
 constexpr unsigned F_ON_T = 1u, F_ON_B = 2u, F_ON_F = 4u, F_ON_P = 8u, F_ON_S = 16u, F_IVAL = 32u, F_NODE = 64u;
+/* 1: the fused passes of the FAST kernels read "variable k is free" from the flag word like every other kernel (rounds 1-7; A/B builds with
+ * tools/build_variant.py, the second build of tests/test_structural_masks_emulation.py).  0: from the structure (Solver::on) */
+#ifndef MSD_FLAG_WORD_MASKS
+#define MSD_FLAG_WORD_MASKS 0
+#endif
 
 /* one field of a node's iterate: CNT doubles, in registers or in the work area (stride NS = node slots of the workgroup) */
 template <int CNT, int NS, bool MEM> struct Field;
@@ -1960,6 +1966,29 @@ struct Solver {
     __device__ __forceinline__ double lbv(int k) const { return k == VT ? U.tlo : k == VB ? U.blo : k == VF ? U.flo : k == VP ? U.plo : U.slo; }
     __device__ __forceinline__ double ubv(int j, int k) const { return k == VT ? U.thi : k == VB ? n[j].ubB : k == VF ? U.fhi : k == VP ? U.phi : INFINITY; }
     __device__ static __forceinline__ bool hasU(int k) { return k != VS; }
+    /* "variable k of node j is free" in the fused passes.  A FAST kernel has the structure compiled in: t is free at every node but the first, b at
+     * every interval but the first, Fel and the loss slack at every interval, Fpb where the structure has the brake -- three lane masks (ival, node,
+     * i > 0) where the flag word's five bits, whose equality the compiler cannot know, cost the hot loop some sixty live masks (round 8).  Start-up
+     * still builds the flag word from the scenario's data; run() compares the two and hands a scenario on which they differ to the general iteration
+     * (structural_start).  Every other kernel, and the general iteration of a FAST one, reads the flag word */
+    static constexpr bool STRUCT_MASKS = full_energy(FULL) && DYN == LOSS_STATIC && !STREAM && !GEN && MSD_PARALLEL_RICCATI && !MSD_FLAG_WORD_MASKS;      /* (FAST && ...) */
+    __device__ __forceinline__ bool on(int j, int k) const
+    {
+        const NodeT &nd = n[j];
+        if constexpr (STRUCT_MASKS) return k == VT ? (nd.node() && nd.i > 0) : k == VB ? (nd.ival() && nd.i > 0) : k == VP ? (full_pn(FULL) && nd.ival()) : nd.ival();
+        else return nd.on(k);
+    }
+    /* the flag words of the scenario are the structural ones (a lane's vote: block_any makes it the workgroup's).  They differ where a variable the
+     * structure has free is fixed by the data: t0 == tEnd, an interior speed limit equal to the minimum speed, f_min == f_max, f_min_pn == 0 */
+    __device__ __forceinline__ bool structural_start() const
+    {
+        bool same = true;
+#pragma unroll
+        for (int j = 0; j < SPT; j++)
+#pragma unroll
+            for (int k = 0; k < NV; k++) same = same && n[j].on(k) == on(j, k);
+        return same;
+    }
 
     /* phase boundary: keeps the optimiser from carrying subexpressions of the state (slacks, reciprocals, Sigma ...) from one
      * phase to the next in registers -- recomputing them is cheaper than the spills they cause */
@@ -2130,20 +2159,22 @@ struct Solver {
 
     /* primal direction and new dynamics multipliers of node j, as the Riccati sweep left them in the node's stage block */
     struct Dir { double dx[NV], lt, lb; };
+    template <bool FUSED = false>      /* (FUSED: called by a fused pass -- the free variables from the structure, on(j, k)) */
     __device__ __forceinline__ void load_dir(int j, Dir &d) const
     {
         const NodeT &nd = n[j];
+        const auto free = [&](int k) { return FUSED ? on(j, k) : nd.on(k); };
 #pragma unroll
         for (int k = 0; k < NV; k++) d.dx[k] = 0;
         d.lt = d.lb = 0;
         if (!nd.node()) return;
         const double *s = c.S + nd.i*S_STRIDE;
-        if (nd.on(VT)) d.dx[VT] = s[S_DT];
-        if (nd.on(VB)) d.dx[VB] = s[S_DB];
+        if (free(VT)) d.dx[VT] = s[S_DT];
+        if (free(VB)) d.dx[VB] = s[S_DB];
         if (nd.ival()) {
-            if (nd.on(VF)) d.dx[VF] = s[S_DF];
-            if (nd.on(VP)) d.dx[VP] = s[S_DP];
-            if (nd.on(VS)) d.dx[VS] = s[S_DS];
+            if (free(VF)) d.dx[VF] = s[S_DF];
+            if (free(VP)) d.dx[VP] = s[S_DP];
+            if (free(VS)) d.dx[VS] = s[S_DS];
             d.lt = s[S_LT]; d.lb = s[S_LB];
         }
     }
@@ -2973,6 +3004,7 @@ struct Solver {
      * repeats the iteration on the general path (run()).
      * ---------------------------------------------------------------------------------------- */
     static constexpr bool FAST = full_energy(FULL) && DYN == LOSS_STATIC && !STREAM && !GEN && MSD_PARALLEL_RICCATI;
+    static_assert(STRUCT_MASKS == (FAST && !MSD_FLAG_WORD_MASKS), "structural lane masks: the kernels with the fused iteration");
     static constexpr int HV = 6;      /* gradient side of a stage block: t, b, q, f, p and the slack row */
     double cnt_lam = 0, cnt_z = 0;    /* numbers of constraint and of bound multipliers (fused_pass) */
 
@@ -3148,7 +3180,7 @@ struct Solver {
 #pragma unroll
                 for (int k = 0; k < NV; k++) {
                     Sv[k] = 0; g1v[k] = 0;
-                    if ((k == VP && !withPn()) || !nd.on(k)) continue;
+                    if ((k == VP && !withPn()) || !on(j, k)) continue;
                     {
                         const double sl = nd.x[k] - lbv(k), z = nd.zL[k], ri = frcp(sl), cp = sl*z;
                         gl[j][k] -= z; cmax = fmax(cmax, cp); cmin = fmin(cmin, cp); sumz += z; nz += 1; prod *= sl;
@@ -3207,7 +3239,7 @@ struct Solver {
             double *sB = c.S + i*S_STRIDE;
             sB[S_HBB] = Hbb; sB[S_HBQ] = Hbq;
 #pragma unroll
-            for (int k = 0; k < NV; k++) if (!(k == VP && !withPn()) && nd.on(k)) dual = fmax(dual, fabs(gl[j][k]));
+            for (int k = 0; k < NV; k++) if (!(k == VP && !withPn()) && on(j, k)) dual = fmax(dual, fabs(gl[j][k]));
         }
         /* the row residuals wait for post_direction in five exchange arrays that are free until the next pass: not in registers
          * across the KKT solve */
@@ -3269,7 +3301,7 @@ struct Solver {
             for (int r = 0; r < NR; r++) nd.dsg[r] = 0;
             if (!nd.node()) continue;
             const int i = nd.i;
-            Dir d; load_dir(j, d);
+            Dir d; load_dir<true>(j, d);
             double og[NV] = {0, 0, 0, 0, 0};
             if (nd.ival()) {
                 const double f = nd.x[VF], sb = c.xs[i], sb1 = c.xs[i + 1];
@@ -3288,7 +3320,7 @@ struct Solver {
             }
 #pragma unroll
             for (int k = 0; k < NV; k++) {
-                if ((k == VP && !withPn()) || !nd.on(k)) continue;
+                if ((k == VP && !withPn()) || !on(j, k)) continue;
                 const double dk = d.dx[k];
                 double gp;
                 {
@@ -3343,7 +3375,7 @@ struct Solver {
 #pragma unroll
         for (int j = 0; j < SPT; j++) {
             node_fence<4>();
-            Dir dd; load_dir(j, dd);
+            Dir dd; load_dir<true>(j, dd);
 #pragma unroll
             for (int k = 0; k < NV; k++) xt[j][k] = step_to(n[j].x[k], alpha, dd.dx[k]);
 #pragma unroll
@@ -3392,7 +3424,7 @@ struct Solver {
             if (nd.node()) {
 #pragma unroll
                 for (int k = 0; k < NV; k++) {
-                    if ((k == VP && !withPn()) || !nd.on(k)) continue;
+                    if ((k == VP && !withPn()) || !on(j, k)) continue;
                     { const double sl = xt[j][k] - lbv(k); if (sl <= 0) bad = 1; else prod *= sl; }
                     if (hasU(k)) { const double su = ubv(j, k) - xt[j][k]; if (su <= 0) bad = 1; else prod *= su; }
                     else damp += xt[j][k] - lbv(k);
@@ -3421,10 +3453,10 @@ struct Solver {
             load_static<4>(j);
             NodeT &nd = n[j];
             if (!nd.node()) continue;
-            Dir dd; load_dir(j, dd);
+            Dir dd; load_dir<true>(j, dd);
 #pragma unroll
             for (int k = 0; k < NV; k++) {
-                if ((k == VP && !withPn()) || !nd.on(k)) continue;
+                if ((k == VP && !withPn()) || !on(j, k)) continue;
                 const double dk = dd.dx[k], xo = nd.x[k], xn = step_to(xo, apr, dk);
                 {
                     const double s = xo - lbv(k), z = nd.zL[k], r = frcp(s);
@@ -3474,7 +3506,7 @@ struct Solver {
                 if (!nd.node()) continue;
 #pragma unroll
                 for (int k = 0; k < NV; k++) {
-                    if ((k == VP && !withPn()) || !nd.on(k)) continue;
+                    if ((k == VP && !withPn()) || !on(j, k)) continue;
                     nd.zL[k] = sigma_clamp(nd.zL[k], mu_, nd.x[k] - lbv(k));
                     if (hasU(k)) nd.zU[k] = sigma_clamp(nd.zU[k], mu_, ubv(j, k) - nd.x[k]);
                 }
@@ -3615,6 +3647,10 @@ struct Solver {
             nd.lam[0] = nd.lam[1] = 0;
             nd.sct = nd.scb = 1;
         }
+        if constexpr (FL && STRUCT_MASKS) {
+            /* the data fix a variable that the structure has free: no fused start for this scenario (reason 0) */
+            if (block_any(!structural_start(), c)) { why_general = 0; iters_out = 0; return STATUS_GENERAL; }
+        }
         double mu = mu_start, tau = fmax(K_TAU_MIN, 1 - mu);
         if (!(RESUMABLE && !FL && resume)) {
         if (!ext && startKind == MSD_START_PROFILE) profile_start(t0, tEnd, v0sq, vNsq);
@@ -3693,7 +3729,7 @@ struct Solver {
             const double *q = dualStart ? dual_in + (size_t)MSD_DUAL_STRIDE*n[j].i : nullptr;
 #pragma unroll
             for (int k = 0; k < NV; k++) {
-                if (!n[j].on(k)) continue;
+                if (!(FL ? on(j, k) : n[j].on(k))) continue;
                 n[j].x[k] = push_in(n[j].x[k], lbv(k), ubv(j, k), true, hasU(k), kp);
                 n[j].zL[k] = warm ? mu_start/(n[j].x[k] - lbv(k)) : 1.0;
                 n[j].zU[k] = hasU(k) ? (warm ? mu_start/(ubv(j, k) - n[j].x[k]) : 1.0) : 0.0;
@@ -4369,10 +4405,17 @@ __device__ __noinline__ int resto_entry(const DevProb *P, Ctx c, double *work, U
  *      list P.follow and left to the follow-up kernel; the code and the registers of the cold paths stay out of this kernel's code object
  *   2  the follow-up: general iteration + restoration phase + second attempt, for the scenarios of the list (P.follow) or, without a
  *      list, for the whole batch (launches none of whose scenarios can start fused: the reference's starting point, a primal-only warm start)
+ *
+ * EARLY -- the first-pass kernels with the fused iteration (FAST, PART 1 or 3) hold the early results (DevProb::done, statsHost, budget) only in the
+ * instantiations with EARLY, which the launch code takes for a begun batch or an iteration budget (msd_api.hip: launch_plan; units msd_kernels_full5.hip,
+ * msd_kernels_full6.hip, msd_kernels_rg3.hip).  In the default instantiations the two flags of the scenario loop and the publishing block cost the hot loop
+ * scalar registers while they never ran (round 7: 301 -> 325 spilled scalars, 1.4 % on config 1) -- like SOCK, an instantiation of its own.  Every other
+ * kernel tests P.done and P.budget at run time, whatever EARLY says.  The body of both: solve_body; solve_kernel is EARLY = false under the symbol names the
+ * kernels have always had, solve_kernel_early the twin
  */
-template <int NT, int SPT, int WPS, int DYN, bool STREAM = false, bool GEN = false, int FULL = 0, int PART = 0, bool SLDS = false, bool SOCK = false>
-__global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, const double *scen, const double *overrides, double *z_out, double *lam_out,
-                                                       double *stats, double *hist, int hist_cap, double *work)
+template <int NT, int SPT, int WPS, int DYN, bool STREAM, bool GEN, int FULL, int PART, bool SLDS, bool SOCK, bool EARLY>
+__device__ __forceinline__ void solve_body(const DevProb &P, int nscen, const double *scen, const double *overrides, double *z_out, double *lam_out,
+                                           double *stats, double *hist, int hist_cap, double *work)
 {
     HIP_DYNAMIC_SHARED(double, lds)
     constexpr int NS = NT*SPT;     /* node slots */
@@ -4394,6 +4437,10 @@ __global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, co
     c.o1 = c.xf + NS; c.o2 = c.o1 + NS; c.o3 = c.o2 + NS;
     using SolverT = Solver<NT, SPT, DYN, STREAM, GEN, FULL, PART, SLDS, SOCK>;
     constexpr bool FASTK = SolverT::FAST;
+#ifndef MSD_EARLY_IN_DEFAULT
+#define MSD_EARLY_IN_DEFAULT 0      /* 1: the default instantiations hold the early results too (round 7's kernels; A/B builds) */
+#endif
+    constexpr bool EARLY_RESULTS = EARLY || MSD_EARLY_IN_DEFAULT || !(FASTK && SolverT::FIRST);      /* (this instantiation holds the early results) */
     c.xs = c.o4 = c.o5 = c.o6 = c.o7 = nullptr;
     if (FASTK) { c.xs = c.o3 + NS; c.o4 = c.xs + NS; c.o5 = c.o4 + NS; c.o6 = c.o5 + NS; c.o7 = c.o6 + NS; }
     if (!STREAM) c.filt = c.o3 + NS + (FASTK ? (XCH_FAST - XCH_GENERAL)*NS : 0);
@@ -4451,7 +4498,7 @@ __global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, co
             Ps.pwU = o[MSD_OV_PW_UPPER]; Ps.pwL = o[MSD_OV_PW_LOWER]; Ps.objDen = o[MSD_OV_OBJ_DEN]; Ps.lossMass = o[MSD_OV_TOTAL_MASS];
         }
         /* iteration budget of a first pass that can hand over: its iteration limit; a scenario that runs into it is the follow-up kernel's (below) */
-        const bool budgeted = SolverT::FIRST && P.follow && P.budget > 0 && P.budget < P.maxIter;
+        const bool budgeted = EARLY_RESULTS && SolverT::FIRST && P.follow && P.budget > 0 && P.budget < P.maxIter;
         if (budgeted) Ps.maxIter = P.budget;
         bool handed = false;      /* the scenario does not end in this kernel (uniform: decided on the uniform status) */
         __syncthreads();
@@ -4558,7 +4605,7 @@ __global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, co
             else startKind = (startKind == MSD_START_PROFILE) ? MSD_START_REFERENCE : MSD_START_PROFILE;
             }
         }
-        if (P.done) {
+        if (EARLY_RESULTS && P.done) {
             /* early results: the scenario has ended here -- z*, the multipliers and the stats record are stored (a barrier follows every run()); the record's
              * mirror, the barrier that puts every wave's stores in front of the word, the word.  The branch is on a kernel argument: uniform */
             const int word = handed ? 0 : (PART == 2 ? 2 : 1);
@@ -4575,6 +4622,19 @@ __global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, co
             if (atomicAdd(P.list + 2, 1) == (int)gridDim.x - 1) { P.list[0] = 0; P.list[1] = 0; P.list[2] = 0; __threadfence(); }
         }
     }
+}
+
+template <int NT, int SPT, int WPS, int DYN, bool STREAM = false, bool GEN = false, int FULL = 0, int PART = 0, bool SLDS = false, bool SOCK = false>
+__global__ void __launch_bounds__(NT, WPS) solve_kernel(DevProb P, int nscen, const double *scen, const double *overrides, double *z_out, double *lam_out,
+                                                       double *stats, double *hist, int hist_cap, double *work)
+{
+    solve_body<NT, SPT, WPS, DYN, STREAM, GEN, FULL, PART, SLDS, SOCK, false>(P, nscen, scen, overrides, z_out, lam_out, stats, hist, hist_cap, work);
+}
+template <int NT, int SPT, int WPS, int DYN, bool STREAM = false, bool GEN = false, int FULL = 0, int PART = 0, bool SLDS = false, bool SOCK = false>
+__global__ void __launch_bounds__(NT, WPS) solve_kernel_early(DevProb P, int nscen, const double *scen, const double *overrides, double *z_out, double *lam_out,
+                                                             double *stats, double *hist, int hist_cap, double *work)
+{
+    solve_body<NT, SPT, WPS, DYN, STREAM, GEN, FULL, PART, SLDS, SOCK, true>(P, nscen, scen, overrides, z_out, lam_out, stats, hist, hist_cap, work);
 }
 
 /* one thread per interval: TrainIntegrator.solve (train.py:347-364) with sensitivities */

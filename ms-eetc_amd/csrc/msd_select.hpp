@@ -32,7 +32,14 @@ inline int structure_of(const msd_problem_desc *d)
     /* power rows (finite by construction: ocp.py:186-187) and finite acceleration bounds (ocp.py:113-114) */
     if (d->has_power_rows == 0 || !std::isfinite(d->acc_min) || !std::isfinite(d->acc_max) || !std::isfinite(d->pw_upper) || !std::isfinite(d->pw_lower)) return 0;
     /* energy objective: both brakes, or the regenerative brake alone (forceMinPn = 0: the reference's scripts) */
-    if (d->energy_optimal != 0) return d->with_pn_brake != 0 ? msd::FULL_BOTH : msd::FULL_RG;
+    if (d->energy_optimal != 0) {
+        /* The fused passes of these kernels take "variable k is free" from the structure (msd_kernel.hpp: Solver::on).  A description that fixes a variable
+         * the structure has free -- no force range, a pneumatic brake without force -- is not of the structure: the general kernels solve it.  Where only a
+         * scenario or an override does that, the kernel hands the scenario over (reason 0); so it does for an interior speed limit equal to the minimum speed,
+         * which is a matter of the profile and not looked for here (the recorded plan table, tests/golden, describes its plans on such a profile) */
+        if (d->f_min == d->f_max || (d->with_pn_brake != 0 && d->f_min_pn == 0.0)) return 0;
+        return d->with_pn_brake != 0 ? msd::FULL_BOTH : msd::FULL_RG;
+    }
     /* the time-optimal problem on the same rolling stock (energyOptimal = False: minimumTime, the twins of msd_mpc.hip): no loss rows */
     return d->with_pn_brake != 0 ? msd::FULL_TIME_BOTH : msd::FULL_TIME_RG;
 }
@@ -64,7 +71,7 @@ inline void fill_problem(msd::DevProb &P, const msd_problem_desc *d)
  * shooting-integrator and integrateLosses families (default there: 128 x 1) */
 struct Tuning {
     bool no_full = false, two_nodes_per_lane = false;
-    int NT = 0, SPT = 0;      /* not 0: every rung offers this geometry instead of its own, whatever the horizon (the emulation's EMU_GEOMETRY=NTxSPT; msd_tuning() does not set it) */
+    int NT = 0, SPT = 0;      /* not 0: every rung offers this geometry instead of its own, whatever the horizon (the emulation's EMU_GEOMETRY=NTxSPT; msd_tuning("geometry", 16 NT + SPT)) */
 };
 
 /* does this build hold the kernel?  Answered by whoever links the instantiations: msd_api.hip (find_kernel over the kernel units), the emulation over its

@@ -114,6 +114,7 @@ def lib():
         L.msd_problem_geometry.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         L.msd_synchronize.argtypes = [vp]
         L.msd_problem_follow_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+        L.msd_problem_last_first_pass.argtypes = [vp, ctypes.c_char_p, ctypes.c_int]
         L.msd_problem_time_first_pass.argtypes = [vp, ctypes.c_int]
         L.msd_problem_first_pass_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
         L.msd_device_alloc.argtypes = [vp, ctypes.c_ulonglong, ctypes.POINTER(vp)]
@@ -516,6 +517,12 @@ class DeviceProblem():
         out = (ctypes.c_int*9)()
         _check(lib().msd_problem_follow_counts(self._h, out, 9))
         return int(out[0]), [int(v) for v in out[1:]]
+
+    def last_first_pass(self):
+        "Symbol name of the first kernel of the handle's last launch ('-': none yet) -- msd_problem_last_first_pass."
+        buf = ctypes.create_string_buffer(512)
+        _check(lib().msd_problem_last_first_pass(self._h, buf, len(buf)))
+        return buf.value.decode()
 
     def timer_begin(self):
         _check(lib().msd_timer_begin(self._h))
