@@ -68,6 +68,14 @@ int msd_problem_last_first_pass(msd_handle h, char *buf, int len);
  */
 int msd_fastmath_probe(int device, int n, const double *x, double *rcp_out, double *sqrt_out, double *rsqrt_out);
 
+/*
+ * Test hook: the reduction over a workgroup that every solver kernel uses (csrc/msd_kernel.hpp: block_reduce<K>), run once by one workgroup of
+ * `nthreads` threads (64, 128 or 256) on K values per thread (K = 1, 2, 4, 5, 6 or 8); op 0: sum, 1: maximum, 2: minimum.  Thread t brings
+ * in[k*nthreads + t], k < K; out[k*nthreads + t] is what it holds afterwards (tests/test_wave_reduce_gpu.py: in every thread bit for bit the balanced
+ * tree over aligned blocks of lanes, the waves' totals folded in their order).  Anything else: MSD_E_INVALID.  Errors: msd_interval_last_error().
+ */
+int msd_reduce_probe(int device, int nthreads, int K, int op, const double *in, double *out);
+
 #ifdef __cplusplus
 }
 #endif

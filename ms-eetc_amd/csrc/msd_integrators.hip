@@ -23,6 +23,7 @@
 #include "../../include/mseetc_hip.h"
 #include "../../include/mseetc_aux.h"
 #include "msd_fastmath.hpp"
+#include "msd_kernel.hpp"      /* (msd_reduce_probe runs the solver kernels' block_reduce; nothing else of it is instantiated here) */
 
 namespace {
 
@@ -307,6 +308,39 @@ __global__ void fastmath_kernel(int n, const double *x, double *rc, double *sq, 
     rs[k] = r;
 }
 
+/* block_reduce<K> of the solver kernels run once by one workgroup of NT threads (msd_reduce_probe): thread t brings in[k*NT + t] and writes back what it holds
+ * afterwards.  NT is a template argument, so that the number of waves is the compile-time constant it is in solve_kernel and block_reduce takes the
+ * single-wave code (wave_reduce_from) or the cross-wave one exactly as it does there.  This unit is compiled without the solver kernels' -fno-unroll-loops;
+ * inside a wave the reductions hold no loop that the unroller decides on (the loops over k are `#pragma unroll`, wave_reduce_from is recursion over
+ * templates); only the fold over the waves' totals may be unrolled here where the kernels loop -- the same operations in the same order */
+template <int NT, int K, class Op> __global__ void __launch_bounds__(NT) reduce_kernel(const double *in, double *out)
+{
+    __shared__ double red[msd::RED_DOUBLES];
+    msd::Ctx c = {};
+    constexpr int nt = NT;
+    c.tid = threadIdx.x; c.lane = threadIdx.x & 63; c.wave = threadIdx.x >> 6; c.nw = NT/64; c.nt = NT; c.red_slot = 0;
+    c.red = red;
+    double v[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) v[k] = in[k*nt + c.tid];
+    msd::block_reduce<K>(v, Op(), c);
+#pragma unroll
+    for (int k = 0; k < K; k++) out[k*nt + c.tid] = v[k];
+}
+
+template <int NT, int K> void launch_reduce_nt(int op, const double *in, double *out)
+{
+    if (op == 0) hipLaunchKernelGGL((reduce_kernel<NT, K, msd::OpSum>), dim3(1), dim3(NT), 0, 0, in, out);
+    else if (op == 1) hipLaunchKernelGGL((reduce_kernel<NT, K, msd::OpMax>), dim3(1), dim3(NT), 0, 0, in, out);
+    else hipLaunchKernelGGL((reduce_kernel<NT, K, msd::OpMin>), dim3(1), dim3(NT), 0, 0, in, out);
+}
+template <int K> void launch_reduce(int nt, int op, const double *in, double *out)
+{
+    if (nt == 64) launch_reduce_nt<64, K>(op, in, out);
+    else if (nt == 128) launch_reduce_nt<128, K>(op, in, out);
+    else launch_reduce_nt<256, K>(op, in, out);
+}
+
 thread_local std::string g_iv_err;
 int iv_fail(int code, const std::string &m) { g_iv_err = m; return code; }
 
@@ -386,6 +420,31 @@ int msd_fastmath_probe(int device, int n, const double *x, double *rcp_out, doub
     }
     double *out[3] = {rcp_out, sqrt_out, rsqrt_out};
     for (int a = 0; a < 3 && e == hipSuccess; a++) e = hipMemcpy(out[a], d + (size_t)(a + 1)*n, sizeof(double)*n, hipMemcpyDeviceToHost);
+    hipFree(d);
+    return e == hipSuccess ? MSD_OK : iv_fail(MSD_E_HIP, hipGetErrorString(e));
+}
+
+int msd_reduce_probe(int device, int nthreads, int K, int op, const double *in, double *out)
+{
+    if (!in || !out || op < 0 || op > 2 || (nthreads != 64 && nthreads != 128 && nthreads != 256)) return iv_fail(MSD_E_INVALID, "bad argument");
+    if (K != 1 && K != 2 && K != 4 && K != 5 && K != 6 && K != 8) return iv_fail(MSD_E_INVALID, "K is one of 1, 2, 4, 5, 6, 8");
+    if (hipSetDevice(device) != hipSuccess) return iv_fail(MSD_E_NODEVICE, "no such device");
+    const size_t n = (size_t)K*nthreads;
+    double *d = nullptr;
+    if (hipMalloc((void **)&d, sizeof(double)*2*n) != hipSuccess) return iv_fail(MSD_E_HIP, "hipMalloc");
+    hipError_t e = hipMemcpy(d, in, sizeof(double)*n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        switch (K) {
+        case 1: launch_reduce<1>(nthreads, op, d, d + n); break;
+        case 2: launch_reduce<2>(nthreads, op, d, d + n); break;
+        case 4: launch_reduce<4>(nthreads, op, d, d + n); break;
+        case 5: launch_reduce<5>(nthreads, op, d, d + n); break;
+        case 6: launch_reduce<6>(nthreads, op, d, d + n); break;
+        default: launch_reduce<8>(nthreads, op, d, d + n); break;
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d + n, sizeof(double)*n, hipMemcpyDeviceToHost);
     hipFree(d);
     return e == hipSuccess ? MSD_OK : iv_fail(MSD_E_HIP, hipGetErrorString(e));
 }

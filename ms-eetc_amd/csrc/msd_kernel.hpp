@@ -519,15 +519,133 @@ enum { PH_EVAL = 0, PH_KKT, PH_ASSEMBLE, PH_RICCATI, PH_READBACK, PH_GPHID, PH_S
  * three phases the fused iteration does not have, and misc[12..14] */
 enum { PH_R_ELEM = PH_EVAL, PH_R_SCAN_P = PH_READBACK, PH_R_RECUR = PH_STEPLEN, PH_R_SCAN_G = 10, PH_R_FEED = 11, PH_R_SCAN_X = 12, PH_SLOTS = 13 };
 
-struct OpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } __device__ static double identity() { return -INFINITY; } };
-struct OpMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } __device__ static double identity() { return INFINITY; } };
-struct OpSum { __device__ double operator()(double a, double b) const { return a + b; } __device__ static double identity() { return 0.0; } };
+/* (grouped: the result depends on how the operands are grouped, so every reduction has to keep the grouping of wave_reduce) */
+struct OpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } __device__ static double identity() { return -INFINITY; } static constexpr bool grouped = false; };
+struct OpMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } __device__ static double identity() { return INFINITY; } static constexpr bool grouped = false; };
+struct OpSum { __device__ double operator()(double a, double b) const { return a + b; } __device__ static double identity() { return 0.0; } static constexpr bool grouped = true; };
+
+/* 1: the reductions of rounds 1-8 in every kernel -- every value on its own through six DPP steps that fill the lanes without a source from a register
+ * holding the identity (wave_reduce; A/B builds with tools/build_variant.py).  0: a workgroup of one wave reduces through wave_reduce_from below.  The
+ * workgroups of several waves keep wave_reduce: with wave_reduce_from the 192 x 3 kernel of the general iteration (N = 560, the reference's starting point)
+ * took 83 iterations, once 32, where it takes 68 -- same optimum, cause not found (profiles/r09/README.md) */
+#ifndef MSD_SERIAL_REDUCE
+#define MSD_SERIAL_REDUCE 0
+#endif
 
 /*
- * Reduction over the 64 lanes of a wave, result in every lane.  On the GPU: DPP moves (row_shr 1/2/4/8 inside the rows of 16 lanes,
- * row_bcast 15 and 31 across them) leave the total in lane 63, v_readlane broadcasts it -- 6 dependent steps of 3 VALU instructions
- * instead of 6 round trips through the LDS crossbar (__shfl_xor = ds_bpermute), and the iteration has some forty of these.
+ * Reduction over the 64 lanes of a wave, result in every lane.  On the GPU the value of lane 63 -- the balanced tree over aligned blocks of lanes:
+ * neighbours, pairs, quads, halves of a row of 16, rows 0+1 and 2+3, the halves of the wave -- broadcast by v_readlane: 6 dependent DPP steps instead of 6
+ * round trips through the LDS crossbar (__shfl_xor = ds_bpermute).  wave_reduce (further down) shifts through the rows and fills the lanes without a source
+ * from a register holding the identity.  wave_reduce_one and wave_reduce_from (single-wave workgroups) load no identity: two v_mov_b32_dpp and the operation
+ * per step; inside a quad both partners exist (quad_perm), a row shift or a row broadcast fills the lanes without a source with 0 (bound_ctrl) -- which is
+ * what a sum adds there anyway, and for a maximum or minimum only spoils lanes that the tree of lane 63 never reads.
+ *
+ * K values at once (wave_reduce_from) go through a transposing butterfly: at a distance a lane keeps one value of a pair and sends the other, so every
+ * step halves the number of values in flight -- 4 values cost 3 + 4 combinations instead of 24, in independent chains.  A sum has to keep the tree's
+ * grouping and therefore transposes at the distances 1 and 2 (two selects and a quad_perm per pair; lane l ends up with value l & 3), then crosses the rows
+ * with the lane swaps of gfx950, which keep a lane's place in its row.  Maxima and minima do not depend on the order and transpose across the halves and
+ * the rows first, where v_permlane32_swap / v_permlane16_swap exchange a pair without any select.  Every total is read from the lane it lands in.
+ * tests/test_wave_reduce_model.py replays these moves lane by lane; tests/test_wave_reduce_gpu.py holds the device to the tree bit for bit.
  */
+#if !defined(MSD_HOST_EMULATION) && !MSD_SERIAL_REDUCE
+/* the value of another lane: every lane's source by the DPP control word CTRL, 0 where a lane has none */
+template <int CTRL> __device__ __forceinline__ double dpp_move(double x)
+{
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+template <int CTRL, class Op> __device__ __forceinline__ double dpp_step(double x, Op op) { return op(x, dpp_move<CTRL>(x)); }
+template <int LANE> __device__ __forceinline__ double lane_value(double x)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), LANE), __builtin_amdgcn_readlane(__double2loint(x), LANE));
+}
+/* HALVES: the upper half of a changes places with the lower half of b (v_permlane32_swap); else rows 1 and 3 of a with rows 0 and 2 of b (v_permlane16_swap) */
+template <bool HALVES> __device__ __forceinline__ void lane_swap(double &a, double &b)
+{
+    typedef unsigned int pair_t __attribute__((ext_vector_type(2)));
+    pair_t lo, hi;
+    if (HALVES) {
+        lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+        hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    } else {
+        lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+        hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    }
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+/* x combined with the x of the lane 16 (HALVES: 32) further on or back: in every lane */
+template <bool HALVES, class Op> __device__ __forceinline__ double swap_combine(double x, Op op)
+{
+    double p = x, q = x;
+    lane_swap<HALVES>(p, q);
+    return op(p, q);
+}
+/* the distances 4 and 8 inside a row: afterwards lane 12 + m of a row holds the lanes 4 q + m of the row, q = 3 ... 0 */
+template <class Op> __device__ __forceinline__ double row_upper_steps(double x, Op op)
+{
+    x = dpp_step<0x114>(x, op);      /* row_shr:4 */
+    return dpp_step<0x118>(x, op);   /* row_shr:8 */
+}
+template <class Op> __device__ __forceinline__ double wave_reduce_one(double x, Op op)
+{
+    x = dpp_step<0xb1>(x, op);       /* quad_perm:[1,0,3,2] */
+    x = dpp_step<0x4e>(x, op);       /* quad_perm:[2,3,0,1] */
+    x = row_upper_steps(x, op);
+    x = dpp_step<0x142>(x, op);      /* row_bcast:15: lanes 31 and 63 hold rows 0+1 and 2+3 */
+    x = dpp_step<0x143>(x, op);      /* row_bcast:31: lane 63 holds the wave */
+    return lane_value<63>(x);
+}
+/* one transposing step inside a quad: of a pair of values the lanes with `upper` keep b and the others a, and each combines it with the partner's */
+template <int CTRL, class Op> __device__ __forceinline__ double dpp_transpose(double a, double b, bool upper, Op op)
+{
+    const double keep = upper ? b : a, send = upper ? a : b;
+    return op(keep, dpp_move<CTRL>(send));
+}
+/* v[O ... K - 1] over the wave, in every lane: four values at once, then two, then one */
+template <int K, int O, class Op> __device__ __forceinline__ void wave_reduce_from(double (&v)[K], Op op, int lane)
+{
+    constexpr bool FOUR = K - O >= 4;
+    if constexpr (K - O >= 2 && !Op::grouped) {
+        lane_swap<true>(v[O], v[O + 1]);
+        double x = op(v[O], v[O + 1]);                  /* lower half: value 0 of the lanes l and l + 32, upper half: value 1 */
+        if constexpr (FOUR) {
+            lane_swap<true>(v[O + 2], v[O + 3]);
+            double y = op(v[O + 2], v[O + 3]);
+            lane_swap<false>(x, y);
+            x = op(x, y);                               /* rows 0 ... 3: values 0, 2, 1, 3 of the four lanes l & 15 */
+        }
+        x = dpp_step<0xb1>(x, op);
+        x = dpp_step<0x4e>(x, op);
+        x = row_upper_steps(x, op);
+        if constexpr (FOUR) {
+            v[O] = lane_value<15>(x); v[O + 1] = lane_value<47>(x); v[O + 2] = lane_value<31>(x); v[O + 3] = lane_value<63>(x);
+        } else {
+            x = dpp_step<0x142>(x, op);
+            v[O] = lane_value<31>(x); v[O + 1] = lane_value<63>(x);
+        }
+        wave_reduce_from<K, O + (FOUR ? 4 : 2)>(v, op, lane);
+    } else if constexpr (K - O >= 2) {
+        double x = dpp_transpose<0xb1>(v[O], v[O + 1], (lane & 1) != 0, op);
+        if constexpr (FOUR) {
+            const double y = dpp_transpose<0xb1>(v[O + 2], v[O + 3], (lane & 1) != 0, op);
+            x = dpp_transpose<0x4e>(x, y, (lane & 2) != 0, op);         /* lane l: value l & 3 of its quad */
+        } else
+            x = dpp_step<0x4e>(x, op);                                /* lane l: value l & 1 of its quad */
+        x = row_upper_steps(x, op);
+        x = swap_combine<false>(x, op);
+        x = swap_combine<true>(x, op);
+        if constexpr (FOUR) {
+            v[O] = lane_value<60>(x); v[O + 1] = lane_value<61>(x); v[O + 2] = lane_value<62>(x); v[O + 3] = lane_value<63>(x);
+        } else {
+            v[O] = lane_value<62>(x); v[O + 1] = lane_value<63>(x);
+        }
+        wave_reduce_from<K, O + (FOUR ? 4 : 2)>(v, op, lane);
+    } else if constexpr (K - O == 1)
+        v[O] = wave_reduce_one(v[O], op);
+}
+#endif
 #ifndef MSD_HOST_EMULATION
 template <int CTRL, int ROW_MASK, class Op> __device__ __forceinline__ double dpp_combine(double x, Op op)
 {
@@ -563,9 +681,12 @@ __device__ __forceinline__ bool wave_any(bool p) { return wave_reduce(p ? 1.0 : 
 
 template <int K, class Op> __device__ __forceinline__ void block_reduce(double (&v)[K], Op op, Ctx &c)
 {
+#if !defined(MSD_HOST_EMULATION) && !MSD_SERIAL_REDUCE
+    if (c.nw == 1) { wave_reduce_from<K, 0>(v, op, c.lane); return; }      /* one wave per workgroup: the result is in every lane */
+#endif
 #pragma unroll
     for (int k = 0; k < K; k++) v[k] = wave_reduce(v[k], op);
-    if (c.nw == 1) return;         /* one wave per workgroup: the wave reduction already left the result in every lane */
+    if (c.nw == 1) return;        /* one wave per workgroup: the wave reduction already left the result in every lane */
     double *buf = c.red + (c.red_slot & (RED_SLOTS - 1))*(MAX_WAVES*RED_K);
     c.red_slot++;
     if (c.lane == 0) {

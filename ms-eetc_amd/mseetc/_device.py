@@ -592,6 +592,26 @@ def fastmath_probe(x, device=0):
     return out
 
 
+def reduce_probe(x, op, device=0):
+    """
+    block_reduce<K> of csrc/msd_kernel.hpp run once by one workgroup (test hook: msd_reduce_probe).  x: (K, nthreads) operands, thread t holding
+    x[:, t]; K in {1, 2, 4, 5, 6, 8}, nthreads in {64, 128, 256}; op 0: sum, 1: maximum, 2: minimum.  Returns (K, nthreads): what every thread holds
+    afterwards.
+    """
+    L = lib()
+    L.msd_reduce_probe.argtypes = [ctypes.c_int]*4 + [_dptr]*2      # (set here: a library of an earlier round, loaded through MSD_LIB, has no such symbol)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    K, nthreads = x.shape
+    out = np.empty_like(x)
+    rc = L.msd_reduce_probe(int(device), nthreads, K, int(op), _d(x), _d(out))
+    if rc != 0:
+        msg = L.msd_interval_last_error().decode()
+        if rc == -1:
+            raise ValueError(msg)
+        raise DeviceError(msg)
+    return out
+
+
 def _check_post(rc):
 
     if rc != 0:
