@@ -62,6 +62,13 @@ int msd_plan_describe(const msd_problem_desc *desc, char *buf, int len);
 int msd_problem_last_first_pass(msd_handle h, char *buf, int len);
 
 /*
+ * The rows of speed limits the handle holds (msd_problem_speed_restrictions), as limit_rows_kernel built them: rows[nscen][N+1] (host), nscen of the call that set
+ * them.  Waits for the handle's stream.  MSD_E_INVALID when the handle holds none.  (tests/test_speed_restrictions_gpu.py: bit for bit the host statement of the
+ * rule, casadiSolver.restrictedLimits)
+ */
+int msd_problem_limit_rows(msd_handle h, double *rows);
+
+/*
  * Test hook: the reciprocal and the square root / reciprocal square root of the fused interior-point iteration (csrc/msd_fastmath.hpp: v_rcp_f64 /
  * v_rsq_f64 refined without the compiler's range scaling) evaluated on n operands, so that the GPU tests can bound their error against the IEEE
  * operations (tests/test_gpu_parity.py::test_fast_reciprocal_and_square_root: <= 1 ulp on normal operands).  Errors: msd_interval_last_error().

@@ -284,6 +284,39 @@ int msd_solve_batch_wait(msd_handle h, int what, int *n_pending);
 int msd_solve_batch_done(msd_handle h, const volatile int **words, const double **stats_now);
 
 /*
+ * Speed restrictions per scenario: the scenarios of a batch differ in their speed limits -- temporary speed restrictions, signal aspects, engineering works as
+ * what-if cases of one launch.  In the reference every such question is a new Track with lowered speedLimits and a new casadiSolver (ocp.py:266-269).  Same grid,
+ * same gradients and curvatures as the handle's problem; every scenario gets a row of limits of its own, built on the device from its records.
+ *
+ * The rule.  A restriction is (begin [m], end [m], velocity [m/s]), positions in the coordinates of the problem's grid (0 = first node; pos[0..N] = running sum
+ * of desc.ds).
+ *   - interval i is restricted if pos[i] < end && pos[i+1] > begin;
+ *   - for 1 <= i <= N-1: row[i] = min(bmax[i], velocity*velocity) if interval i-1 or interval i is restricted, else bmax[i];
+ *   - several restrictions take the minimum;
+ *   - row[0] and row[N] are copies of the problem's entries.
+ * That is the reference's min(vlim_i, vmax, vlim_{i-1})^2 with vlim lowered on the restricted intervals.  The grid does NOT gain the end points of a restriction
+ * as nodes: a restriction lowers the limit on every interval it touches.  That is the difference to building a new Track, whose breakpoints become nodes.
+ *
+ *   count   [nscen]                                       restrictions of scenario k, 0 ... max_per_scenario
+ *   records [nscen][max_per_scenario][MSD_RS_COUNT]       host; entries behind a scenario's count are ignored
+ *
+ * The rows are state of the handle, like msd_problem_early_results: after the call every launch of the handle with exactly nscen scenarios -- msd_solve_batch,
+ * _ex, _warm, _shifted, _device, _device_ex, _begin -- solves scenario k under row k, in both kernels of a split launch; a launch with another nscen returns
+ * MSD_E_INVALID.  nscen = 0 clears the rows (count and records may be NULL then), and so does msd_problem_reconfigure.  msd_solve_batch_multi: every handle
+ * holds the rows of its own slice, the caller sets them per handle.  The loops of mseetc_mpc.h keep their own problem records and are not affected.  Not between
+ * msd_solve_batch_begin and MSD_WAIT_ALL.  The call waits for the handle's stream, uploads the records and builds the rows on the stream without waiting again.
+ * The scenario records stay the caller's: the caller clips v0 and vN to the restricted limit of the first and the last interval (mseetc/ocp.py does).
+ *
+ * MSD_E_INVALID (text in msd_last_error(); the rows the handle held stay as they were): a null pointer; max_per_scenario outside 1 ... MSD_RS_MAX; a count outside
+ * 0 ... max_per_scenario; a record that is not finite; end <= begin; a record that restricts no interval of the grid; velocity <= 0 or velocity^2 <= vmin_sq.
+ * The last one excludes a limit equal to the minimum speed: it fixes b at two or more adjacent nodes, and no such problem tried on the CPU oracle reached a
+ * solution from either starting point at any running time; this version does not support it.
+ */
+#define MSD_RS_COUNT 3      /* begin [m], end [m], velocity [m/s] */
+#define MSD_RS_MAX   16     /* restrictions per scenario */
+int msd_problem_speed_restrictions(msd_handle h, int nscen, int max_per_scenario, const int *count, const double *records);
+
+/*
  * The other two interval integrators of TrainIntegrator (mseetc/train.py:303-322) for n independent intervals -- what
  * TrainIntegrator(model, 'CVODES' | 'IRK', opts).solve(...) (train.py:347-364) evaluates, e.g. in simulations/figure4.py.
  *   train5 : sr0, sr1, sr2, g, rho

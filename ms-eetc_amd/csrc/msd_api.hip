@@ -254,6 +254,7 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
     P.dualIn = ws.d_dual_in; P.dualInStride = ws.dual_stride; P.dualShift = ws.dual_shift; P.dualOut = ws.d_dual_out;
     P.oneAttempt = ws.one_attempt ? 1 : 0;
     P.done = ws.d_done; P.statsHost = ws.d_stats_host; P.budget = ws.budget;
+    P.limits = ws.d_limits;      /* (both kernels of a split launch, and a list-driven one: a list holds original scenario indices, so row k stays with scenario k) */
     const bool split = pl.kernel2 != nullptr;
     const bool plain = !pl.fused_family || (ws.d_guess ? ws.d_dual_in != nullptr : P.start == MSD_START_PROFILE);      /* no multiplier estimate needed */
     const bool first_pass = split && (plain || pl.kernel_lsq != nullptr);
@@ -316,6 +317,34 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
 }  // namespace msd_host
 
 using msd_host::check_desc;
+
+namespace {
+/*
+ * Rows of speed limits per scenario from the scenarios' restriction records (the rule of include/mseetc_hip.h: msd_problem_speed_restrictions).  One workgroup
+ * per scenario, threads strided over the nodes: the scenario's records are the same for every thread (scalar loads), the row is stored coalesced.
+ * v*v is one rounded product in double, the host rule's (mseetc/ocp.py: restrictedLimits).
+ *   records [nscen][max_per][MSD_RS_COUNT], count [nscen], bmax / pos [N+1] of the problem, rows [nscen][N+1]
+ */
+__global__ void __launch_bounds__(256) limit_rows_kernel(int N, int max_per, const double *bmax, const double *pos, const double *records, const int *count, double *rows)
+{
+    const int k = blockIdx.x;
+    const int n = count[k];
+    const double *rec = records + (size_t)MSD_RS_COUNT*max_per*k;
+    double *row = rows + (size_t)(N + 1)*k;
+    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
+        double b = bmax[i];
+        if (i >= 1 && i < N) {
+            const double p0 = pos[i - 1], p1 = pos[i], p2 = pos[i + 1];
+            for (int j = 0; j < n; j++) {
+                const double begin = rec[MSD_RS_COUNT*j], end = rec[MSD_RS_COUNT*j + 1], v = rec[MSD_RS_COUNT*j + 2];
+                /* interval i-1 or interval i is restricted */
+                if ((p0 < end && p1 > begin) || (p1 < end && p2 > begin)) b = fmin(b, __dmul_rn(v, v));
+            }
+        }
+        row[i] = b;
+    }
+}
+}  // namespace
 
 extern "C" {
 
@@ -386,6 +415,9 @@ static int configure(msd_problem *h, const msd_problem_desc *d)
     }
     msd_host::pack_profile(d, h->h_stage);
     HIP_TRY(hipMemcpyAsync(h->d_prof, h->h_stage, sizeof(double)*len, hipMemcpyHostToDevice, h->stream));
+    /* another problem: the rows of speed limits per scenario are gone; the node positions stay on the host for the checks of msd_problem_speed_restrictions */
+    h->limit_nscen = 0;
+    h->h_pos.assign(h->h_stage + 4*(size_t)N + 1, h->h_stage + len);
     if (d->loss_kind == 2) {
         if (d->loss_table_len > h->cap_loss) {
             hipFree(h->d_loss); h->d_loss = nullptr; h->cap_loss = 0;
@@ -468,6 +500,7 @@ int msd_problem_destroy(msd_handle h)
     hipFree(h->d_prof); hipFree(h->d_loss); hipFree(h->d_work); hipFree(h->d_queue); hipFree(h->d_follow);
     hipFree(h->d_scen); hipFree(h->d_ovr); hipFree(h->d_z); hipFree(h->d_lam); hipFree(h->d_stats); hipFree(h->d_hist); hipFree(h->d_guess); hipFree(h->d_eval);
     hipFree(h->d_z2); hipFree(h->d_stats2); hipFree(h->d_dual); hipFree(h->d_dual2); hipFree(h->d_coll);
+    hipFree(h->d_limits); hipFree(h->d_rs);
     if (h->h_stage) hipHostFree(h->h_stage);
     if (h->h_soc_seen) hipHostFree((void *)h->h_soc_seen);
     if (h->h_done) hipHostFree((void *)h->h_done);
@@ -489,6 +522,15 @@ constexpr int QUEUE_RING = 64;
 
 using msd_host::WarmStart;
 
+/* rows of speed limits per scenario (msd_problem_speed_restrictions) belong to a batch size: a launch of another one has no row for its scenarios */
+static int check_limit_rows(msd_handle h, int nscen)
+{
+    if (h->limit_nscen && nscen != h->limit_nscen)
+        return fail(MSD_E_INVALID, "the handle holds speed restrictions for " + std::to_string(h->limit_nscen) + " scenarios, the launch has " + std::to_string(nscen) +
+                                   " (msd_problem_speed_restrictions with nscen = 0 clears them)");
+    return MSD_OK;
+}
+
 static int launch(msd_handle h, int nscen, const double *d_scen, const double *d_ovr, double *d_z, double *d_lam, double *d_stats, double *d_hist, int hist_cap,
                   const WarmStart &ws_in = WarmStart())
 {
@@ -498,8 +540,11 @@ static int launch(msd_handle h, int nscen, const double *d_scen, const double *d
      * behind a 6.3 ms first pass).  A handle whose launches have met one takes the first-pass kernel with the correction inside the fused iteration from
      * then on (msd_kernel.hpp: SOCK; 4 % slower per iteration, no tail); the kernels report it through a word of mapped host memory, read here without
      * waiting for anything */
+    int rc = check_limit_rows(h, nscen);
+    if (rc != MSD_OK) return rc;
     WarmStart ws = ws_in;
     ws.budget = h->budget;
+    ws.d_limits = h->limit_nscen ? h->d_limits : nullptr;
     if (h->plan.kernel_soc) {
         ws.d_soc_seen = h->d_soc_seen;
         if (*h->h_soc_seen != 0) ws.use_soc = true;
@@ -691,6 +736,8 @@ static int enqueue_batch(msd_handle h, int nscen, const double *scen, const doub
                          double *z_out, double *lam_out, double *stats, int shift = -1, bool defer_downloads = false, bool early = false)
 {
     HIP_TRY(hipSetDevice(h->device));
+    int rc_rows = check_limit_rows(h, nscen);      /* (in front of the uploads: a refused batch enqueues nothing) */
+    if (rc_rows != MSD_OK) return rc_rows;
     const size_t nz = h->plan.nz;
     if (nscen > h->cap_scen) {
         hipFree(h->d_scen); hipFree(h->d_ovr); hipFree(h->d_z); hipFree(h->d_lam); hipFree(h->d_stats); hipFree(h->d_z2); hipFree(h->d_stats2);
@@ -806,6 +853,78 @@ int msd_problem_iteration_budget(msd_handle h, int budget)
     if (!h) return fail(MSD_E_INVALID, "null handle");
     if (budget < 0) return fail(MSD_E_INVALID, "the iteration budget of the first pass must not be negative (0: none)");
     h->budget = budget;
+    return MSD_OK;
+}
+
+int msd_problem_speed_restrictions(msd_handle h, int nscen, int max_per_scenario, const int *count, const double *records)
+{
+    if (!h) return fail(MSD_E_INVALID, "null handle");
+    if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
+    if (nscen == 0) { h->limit_nscen = 0; return MSD_OK; }      /* (the buffers stay; a launch in flight still reads its rows) */
+    if (!h->plan.kernel) return fail(MSD_E_INVALID, "the handle holds no problem: its last (re)configuration failed");
+    if (nscen < 0 || !count || !records) return fail(MSD_E_INVALID, "msd_problem_speed_restrictions: bad argument");
+    if (max_per_scenario < 1 || max_per_scenario > MSD_RS_MAX)
+        return fail(MSD_E_INVALID, "msd_problem_speed_restrictions: max_per_scenario must be 1 ... " + std::to_string(MSD_RS_MAX));
+    const int N = h->plan.P.N;
+    const double first = h->h_pos[0], last = h->h_pos[N];
+    for (int k = 0; k < nscen; k++) {
+        const auto bad = [&](int j, const char *what) {
+            return fail(MSD_E_INVALID, "speed restriction " + std::to_string(j) + " of scenario " + std::to_string(k) + " " + what);
+        };
+        if (count[k] < 0 || count[k] > max_per_scenario) return fail(MSD_E_INVALID, "scenario " + std::to_string(k) + ": the number of speed restrictions must be 0 ... max_per_scenario");
+        for (int j = 0; j < count[k]; j++) {
+            const double *r = records + (size_t)MSD_RS_COUNT*((size_t)max_per_scenario*k + j);
+            const double begin = r[0], end = r[1], v = r[2];
+            if (!std::isfinite(begin) || !std::isfinite(end) || !std::isfinite(v)) return bad(j, "is not finite");
+            if (!(end > begin)) return bad(j, "ends at or before its beginning");
+            /* some interval i has pos[i] < end && pos[i+1] > begin  <=>  the restriction overlaps (pos[0], pos[N]): the nodes are increasing */
+            if (!(end > first && begin < last)) return bad(j, "restricts no interval of the grid");
+            if (!(v > 0) || !(v*v > h->plan.P.vminSq)) return bad(j, "is not above the minimum speed (a limit equal to it fixes adjacent nodes: not supported)");
+        }
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    /* whatever of the handle is in flight has ended before its rows, the records or the staging buffer are written (the profile upload of a configuration just
+     * made reads that buffer) */
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->limit_nscen = 0;      /* (until the new rows are enqueued: a HIP failure below leaves the handle without rows, not with half of them) */
+    const size_t rec_doubles = (size_t)MSD_RS_COUNT*max_per_scenario*nscen;
+    const size_t rec_bytes = sizeof(double)*rec_doubles + sizeof(int)*(size_t)nscen;      /* records, then the counts */
+    const size_t row_doubles = (size_t)(N + 1)*nscen;
+    if (rec_bytes > h->cap_rs) {
+        hipFree(h->d_rs); h->d_rs = nullptr; h->cap_rs = 0;
+        HIP_TRY(hipMalloc((void **)&h->d_rs, rec_bytes));
+        h->cap_rs = rec_bytes;
+    }
+    if (row_doubles > h->cap_limits) {
+        hipFree(h->d_limits); h->d_limits = nullptr; h->cap_limits = 0;
+        HIP_TRY(hipMalloc((void **)&h->d_limits, sizeof(double)*row_doubles));
+        h->cap_limits = row_doubles;
+    }
+    const size_t stage_doubles = (rec_bytes + sizeof(double) - 1)/sizeof(double);
+    if (stage_doubles > h->cap_stage) {
+        if (h->h_stage) hipHostFree(h->h_stage);
+        h->h_stage = nullptr; h->cap_stage = 0;
+        HIP_TRY(hipHostMalloc((void **)&h->h_stage, sizeof(double)*stage_doubles, hipHostMallocDefault));
+        h->cap_stage = stage_doubles;
+    }
+    memcpy(h->h_stage, records, sizeof(double)*rec_doubles);
+    memcpy(h->h_stage + rec_doubles, count, sizeof(int)*(size_t)nscen);
+    HIP_TRY(hipMemcpyAsync(h->d_rs, h->h_stage, rec_bytes, hipMemcpyHostToDevice, h->stream));
+    /* the rows are built on the device, behind the upload on the handle's stream: the launches that follow are ordered behind the kernel */
+    hipLaunchKernelGGL(limit_rows_kernel, dim3(nscen), dim3(N + 1 < 256 ? 64*((N + 64)/64) : 256), 0, h->stream, N, max_per_scenario, h->plan.P.bmax, h->plan.P.pos,
+                       (const double *)h->d_rs, (const int *)(h->d_rs + rec_doubles), h->d_limits);
+    HIP_TRY(hipGetLastError());
+    h->limit_nscen = nscen;
+    return MSD_OK;
+}
+
+int msd_problem_limit_rows(msd_handle h, double *rows)
+{
+    if (!h || !rows) return fail(MSD_E_INVALID, "bad argument");
+    if (!h->limit_nscen) return fail(MSD_E_INVALID, "the handle holds no speed restrictions (msd_problem_speed_restrictions)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(rows, h->d_limits, sizeof(double)*(size_t)(h->plan.P.N + 1)*h->limit_nscen, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MSD_OK;
 }
 

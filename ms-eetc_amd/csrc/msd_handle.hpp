@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <vector>
 
 #include "msd_kernel.hpp"
 #include "msd_geometry.hpp"
@@ -68,7 +69,8 @@ struct WarmStart { const double *d_guess = nullptr; long long stride = 0; const 
                    bool use_soc = false;             /* the first-pass kernel with the second-order correction inside (Plan::kernel_soc), where the plan has one */
                    int *d_soc_seen = nullptr;        /* DevProb::socSeen of the launch (device address of a mapped host word) */
                    int *d_done = nullptr; double *d_stats_host = nullptr;      /* DevProb::done, statsHost: early results (msd_solve_batch_begin) */
-                   int budget = 0; };                /* DevProb::budget (msd_problem_iteration_budget) */
+                   int budget = 0;                   /* DevProb::budget (msd_problem_iteration_budget) */
+                   const double *d_limits = nullptr; };      /* DevProb::limits: rows of speed limits per scenario (msd_problem_speed_restrictions) */
 
 /*
  * One batch on `stream`: the first pass + the follow-up kernel of a split solve, or the one kernel that holds everything.
@@ -133,6 +135,12 @@ struct msd_problem {
     int begun = 0;                                      /* scenarios of the batch begun and not yet waited for in full (0: none) */
     hipEvent_t ev_first = nullptr;                      /* behind the first kernel of the begun batch */
     msd::KernelFn last_first = nullptr;                 /* the first kernel of the handle's last launch (msd_problem_last_first_pass) */
-    int attached_loops = 0;                             /* receding-horizon loops (msd_mpc_create) that run on this handle's stream: it cannot be destroyed while one exists */
+    /* speed limits of their own per scenario (msd_problem_speed_restrictions): the records as uploaded (counts behind them) and the rows limit_rows_kernel builds from
+     * them, grow-only; limit_nscen scenarios have rows (0: none) and only a launch of exactly that many scenarios is accepted */
+    double *d_rs = nullptr, *d_limits = nullptr;
+    size_t cap_rs = 0, cap_limits = 0;                  /* bytes of d_rs, doubles of d_limits */
+    int limit_nscen = 0;
+    std::vector<double> h_pos;                          /* node positions of the problem the handle holds (the checks of the records) */
+    int attached_loops = 0;                            /* receding-horizon loops (msd_mpc_create) that run on this handle's stream: it cannot be destroyed while one exists */
 };
 

@@ -119,6 +119,8 @@ struct DevProb {
     double *statsHost;       /* not null (with done): mapped host mirror of the stats records, a scenario's record written in front of its word */
     int budget;              /* > 0: iterations a first pass spends on a scenario before it hands it over (reason 7) to the follow-up kernel, which solves it from its
                               * starting point under the problem's own iteration limit; 0: none */
+    const double *limits;    /* not null: speed limits of their own per scenario, [nscen][N+1] rows in the layout of bmax (msd_problem_speed_restrictions); solve_body points
+                              * the bmax of a scenario's LDS copy of this record at the scenario's row.  (With this field the record fills the room UNI_OFF leaves for it) */
 };
 /* behind the three counters: telemetry that is never reset -- [3] scenarios listed so far, [4 + why] by reason: 0 no fused start for the scenario
  * (a warm start whose previous solve failed; a scenario or an override that fixes a variable the compiled-in structure has free -- t0 == tEnd, f_min == f_max,
@@ -4618,6 +4620,8 @@ __device__ __forceinline__ void solve_body(const DevProb &P, int nscen, const do
             Ps.fmax = o[MSD_OV_F_MAX]; Ps.fmin = o[MSD_OV_F_MIN]; Ps.fminPn = o[MSD_OV_F_MIN_PN];
             Ps.pwU = o[MSD_OV_PW_UPPER]; Ps.pwL = o[MSD_OV_PW_LOWER]; Ps.objDen = o[MSD_OV_OBJ_DEN]; Ps.lossMass = o[MSD_OV_TOTAL_MASS];
         }
+        /* per-scenario speed limits: the scenario's own row in place of the problem's (sidx is uniform: the pointer stays scalar) */
+        if (P.limits) Ps.bmax = P.limits + (size_t)(P.N + 1)*sidx;
         /* iteration budget of a first pass that can hand over: its iteration limit; a scenario that runs into it is the follow-up kernel's (below) */
         const bool budgeted = EARLY_RESULTS && SolverT::FIRST && P.follow && P.budget > 0 && P.budget < P.maxIter;
         if (budgeted) Ps.maxIter = P.budget;

@@ -57,6 +57,7 @@ inline void fill_problem(msd::DevProb &P, const msd_problem_desc *d)
     P.vminSq = d->vmin_sq; P.objDen = d->obj_den; P.tol = d->tol;
     P.guess = nullptr; P.guessStride = 0; P.guessStatus = nullptr; P.warmMu = 0; P.warmPush = 0; P.start = d->start_kind; P.lossMass = 0; P.queue = nullptr; P.follow = nullptr; P.list = nullptr; P.socSeen = nullptr; P.done = nullptr; P.statsHost = nullptr; P.budget = 0; P.dualOut = nullptr; P.dualIn = nullptr; P.dualInStride = 0; P.dualShift = 0;
     P.ds = P.grad = P.curv = P.bmax = P.pos = nullptr;
+    P.limits = nullptr;
     P.loss = nullptr; P.lossCoef = nullptr;
     P.integ = d->integrator; P.collD = d->coll_degree; P.newtonIters = d->newton_iterations; P.intAtol = d->int_abstol; P.intRtol = d->int_reltol;
     P.coll = nullptr;

@@ -20,6 +20,7 @@ ST = dict(STATUS=0, ITERS=1, OBJ=2, KKT=3, MU=4, DUAL_INF=5, CONSTR_VIOL=6, COMP
 # (ITERS counts both attempts of a solve that was repeated from the other starting point: after a breakdown, or after the iteration limit behind a
 #  restoration phase -- it can reach twice max_iterations then)
 SC_COUNT = 4
+RS_COUNT, RS_MAX = 3, 16      # MSD_RS_*: (begin [m], end [m], velocity [m/s]) of a speed restriction, restrictions per scenario
 OV = dict(SR0=0, SR1=1, SR2=2, F_MAX=3, F_MIN=4, F_MIN_PN=5, PW_UPPER=6, PW_LOWER=7, OBJ_DEN=8, TOTAL_MASS=9, COUNT=10)
 HIST_COLS = 8
 
@@ -321,6 +322,7 @@ class DeviceProblem():
         self.rowsPerInterval = L.msd_problem_rows_per_interval(self._h)
         self.device = device
         self._results = _ResultArrays()
+        self._limit_rows = 0      # scenarios the handle holds rows of speed limits for (speed_restrictions)
         self.direct_results(True)      # (the result arrays below are page-locked: the kernels store z* there themselves)
 
     def reconfigure(self, desc):
@@ -328,6 +330,7 @@ class DeviceProblem():
 
         L = lib()
         _check(L.msd_problem_reconfigure(self._h, ctypes.byref(desc)))
+        self._limit_rows = 0      # (a reconfiguration clears the rows)
         self.desc = desc
         self.N = desc.num_intervals
         self.nz = L.msd_problem_nz(self._h)
@@ -403,6 +406,39 @@ class DeviceProblem():
 
         _check(lib().msd_problem_iteration_budget(self._h, int(k)))
         return self
+
+    def speed_restrictions(self, count, records=None):
+        """
+        Speed limits of their own per scenario (msd_problem_speed_restrictions): count (B,) restrictions of every scenario, records
+        (B, M, RS_COUNT) rows of (begin [m], end [m], velocity [m/s]), M <= RS_MAX; the device builds the (B, N + 1) rows of limits from them and
+        every launch of exactly B scenarios solves scenario k under row k until the rows are cleared.  count None: clears them.
+        """
+
+        L = lib()
+        L.msd_problem_speed_restrictions.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _dptr]      # (set here, like reduce_probe's)
+        if count is None:
+            _check(L.msd_problem_speed_restrictions(self._h, 0, 1, None, None))
+            self._limit_rows = 0
+            return self
+        count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        B = count.shape[0]
+        records = np.ascontiguousarray(records, dtype=np.float64)
+        if records.ndim != 3 or records.shape[0] != B or records.shape[2] != RS_COUNT:
+            raise ValueError("speed restriction records must have shape ({}, M, {})!".format(B, RS_COUNT))
+        _check(L.msd_problem_speed_restrictions(self._h, B, int(records.shape[1]), count.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _d(records)))
+        self._limit_rows = B
+        return self
+
+    def limit_rows(self, B):
+        "The (B, N + 1) rows of limits the device built from the speed restrictions (msd_problem_limit_rows: waits for the handle's stream)."
+
+        L = lib()
+        L.msd_problem_limit_rows.argtypes = [ctypes.c_void_p, _dptr]
+        if int(B) != self._limit_rows:
+            raise ValueError("the handle holds the rows of {} scenarios, not of {}!".format(self._limit_rows, int(B)))
+        rows = np.zeros((int(B), self.N + 1))
+        _check(L.msd_problem_limit_rows(self._h, _d(rows)))
+        return rows
 
     def early_results(self, on=True):
         "Completion words per scenario for solve_batch_begin (msd_problem_early_results)."

@@ -247,11 +247,19 @@ class casadiSolver():
 
     # ---- scenarios --------------------------------------------------------------------------
 
-    def _scenarios(self, terminalTime, initialTime, terminalVelocity, initialVelocity):
-        "(B,4) records (t0, T, v0^2, vN^2) with the reference's checks and clipping (ocp.py:314-320, 343-344)."
+    def _scenarios(self, terminalTime, initialTime, terminalVelocity, initialVelocity, restrictions=None):
+        """
+        (B,4) records (t0, T, v0^2, vN^2) with the reference's checks and clipping (ocp.py:314-320, 343-344); under speed restrictions
+        (the record of _restrictions) the end speeds are clipped to the restricted limit of the first and of the last interval, per scenario.
+        """
 
-        T, t0, vN, v0 = np.broadcast_arrays(*[np.atleast_1d(np.asarray(a, dtype=float)) for a in
-                                               (terminalTime, initialTime, terminalVelocity, initialVelocity)])
+        first, last = (np.inf, np.inf) if restrictions is None else (restrictions['interval'][:, 0], restrictions['interval'][:, -1])
+
+        try:
+            T, t0, vN, v0, first, last = np.broadcast_arrays(*[np.atleast_1d(np.asarray(a, dtype=float)) for a in
+                                                               (terminalTime, initialTime, terminalVelocity, initialVelocity, first, last)])
+        except ValueError:
+            raise ValueError("The scenarios and the speed restrictions do not have the same batch length!")
 
         if np.any(~np.isfinite(t0)) or np.any(t0 < 0):
             raise ValueError("Initial time must be a positive number, not {}!".format(initialTime))
@@ -261,10 +269,80 @@ class casadiSolver():
 
         vlim = self.points['Speed limit [m/s]'].values
 
-        v0 = np.minimum(np.maximum(v0, self.velocityMin), vlim[0])
-        vN = np.minimum(np.maximum(vN, self.velocityMin), vlim[-1])
+        v0 = np.minimum(np.maximum(v0, self.velocityMin), np.minimum(vlim[0], first))
+        vN = np.minimum(np.maximum(vN, self.velocityMin), np.minimum(vlim[-1], last))
 
         return np.stack([t0, T, v0**2, vN**2], axis=1)
+
+    # ---- speed restrictions per scenario ------------------------------------------------------
+
+    def _restrictions(self, speedRestrictions):
+        """
+        Speed restrictions as the device takes them (include/mseetc_hip.h: msd_problem_speed_restrictions), validated like there.
+        `speedRestrictions`: a sequence of B sequences of (begin [m], end [m], velocity [m/s]), or one such sequence for every scenario; positions
+        in the coordinates of the grid (self.points.index).  Returns dict: 'count' (Bs,), 'records' (Bs, M, 3), 'interval' (Bs, N): the lowest
+        restriction on every interval [m/s] (inf: none); Bs = 1 for a single sequence.  A record of this method passes through.
+        """
+
+        if isinstance(speedRestrictions, dict):
+            return speedRestrictions
+
+        sets = list(speedRestrictions)
+        triple = lambda e: np.ndim(e) == 1 and len(e) == _device.RS_COUNT
+        if all(triple(e) for e in sets):      # (one sequence of restrictions -- an empty one too -- for the whole batch)
+            sets = [sets]
+        if not all(all(triple(e) for e in one) for one in sets):
+            raise ValueError("Speed restrictions are given as (begin [m], end [m], velocity [m/s])!")
+
+        N = self.numIntervals
+        pos = self.points.index.values.astype(float)
+        count = np.array([len(one) for one in sets], dtype=np.int32)
+        if count.max(initial=0) > _device.RS_MAX:
+            raise ValueError("At most {} speed restrictions per scenario!".format(_device.RS_MAX))
+        records = np.zeros((len(sets), max(1, int(count.max(initial=0))), _device.RS_COUNT))
+        interval = np.full((len(sets), N), np.inf)
+
+        for k, one in enumerate(sets):
+            for j, rec in enumerate(one):
+                begin, end, velocity = [float(x) for x in rec]
+                if not np.all(np.isfinite([begin, end, velocity])):
+                    raise ValueError("Speed restriction {} of scenario {} is not finite!".format(j, k))
+                if end <= begin:
+                    raise ValueError("Speed restriction {} of scenario {} ends at or before its beginning!".format(j, k))
+                hit = (pos[:-1] < end) & (pos[1:] > begin)
+                if not hit.any():
+                    raise ValueError("Speed restriction {} of scenario {} restricts no interval of the grid!".format(j, k))
+                if velocity <= 0 or velocity*velocity <= float(self.velocityMin)**2:
+                    raise ValueError("Speed restriction {} of scenario {} is not above the minimum velocity!".format(j, k))
+                records[k, j] = begin, end, velocity
+                interval[k, hit] = np.minimum(interval[k, hit], velocity)
+
+        return dict(count=count, records=records, interval=interval)
+
+    @staticmethod
+    def _restrictionsOf(rs, B, rows=None):
+        "The record of _restrictions for a batch of B scenarios (a single set is repeated), or for its scenarios `rows`."
+
+        if rs['count'].shape[0] not in (1, B):
+            raise ValueError("{} sets of speed restrictions for a batch of {} scenarios!".format(rs['count'].shape[0], B))
+        full = {k: np.ascontiguousarray(np.broadcast_to(v, (B,) + v.shape[1:])) for k, v in rs.items()}
+        return full if rows is None else {k: np.ascontiguousarray(v[rows]) for k, v in full.items()}
+
+    def restrictedLimits(self, speedRestrictions, B):
+        """
+        (B, N+1) upper bounds of b = v^2 under speed restrictions, the rule of include/mseetc_hip.h: interval i is restricted if
+        pos[i] < end and pos[i+1] > begin; for 1 <= i <= N-1 row[i] = min(bmax[i], velocity^2) if interval i-1 or interval i is restricted (several
+        restrictions: the minimum), row[0] and row[N] are the problem's.  That is the reference's min(vlim_i, vmax, vlim_{i-1})^2 (ocp.py:266-269) with
+        vlim lowered on the restricted intervals -- on the grid of this problem: the end points of a restriction do not become nodes.
+        """
+
+        N = self.numIntervals
+        rs = self._restrictionsOf(self._restrictions(speedRestrictions), int(B))
+        rows = np.repeat(np.asarray(self._desc._keep[3], dtype=float)[None, :], int(B), axis=0)
+        v = np.minimum(rs['interval'][:, 0:N - 1], rs['interval'][:, 1:N])
+        rows[:, 1:N] = np.minimum(rows[:, 1:N], v*v)
+
+        return rows
 
     def _overrides(self, B, mass, r0, r1, r2):
         """
@@ -301,7 +379,7 @@ class casadiSolver():
 
     def solveBatch(self, terminalTime, initialTime=0, terminalVelocity=1, initialVelocity=1, multipliers=False,
                    mass=None, r0=None, r1=None, r2=None, guess=None, warmMu=1e-2, warmPush=1e-3, devices=None, classifyFailures=True, shift=None,
-                   onFirstPass=None):
+                   onFirstPass=None, speedRestrictions=None):
         """
         Solve many scenarios of this problem in one launch.  Arguments broadcast against each other; `mass`, `r0`, `r1`, `r2`
         (SI units, scalars or one value per scenario) perturb the rolling stock per scenario.  `guess` (B, nz) or (nz,), in the
@@ -313,13 +391,47 @@ class casadiSolver():
         kernel may still work on the stragglers: `mask` (B,) marks the scenarios that have ended, `partialResult` holds 'z', 'status',
         'iterations', 'cost', 'stats' and 'lam_g', valid where the mask is true (failures there are not classified yet).  The return value is the same
         as without it.  Not combined with `guess`, `shift` or `devices`.
+        `speedRestrictions`: speed limits of their own per scenario -- a sequence of B sequences of (begin [m], end [m], velocity [m/s]) in the
+        coordinates of the grid (self.points.index), or one such sequence for every scenario: temporary speed restrictions, signal aspects,
+        engineering works as what-if cases of one launch.  Scenario k is solved under restrictedLimits(...)[k] on the problem's own grid (the end
+        points of a restriction do not become nodes), its end speeds clipped to the restricted limits.  ValueError: a record that is not finite, ends
+        at or before its beginning, restricts no interval or is not above the minimum velocity; more than 16 per scenario; a wrong batch length.
         """
 
-        scen = self._scenarios(terminalTime, initialTime, terminalVelocity, initialVelocity)
+        rs = self._restrictions(speedRestrictions) if speedRestrictions is not None else None
+
+        scen = self._scenarios(terminalTime, initialTime, terminalVelocity, initialVelocity, rs)
 
         B = max([scen.shape[0]] + [np.size(a) for a in (mass, r0, r1, r2) if a is not None])
         if scen.shape[0] != B:
             scen = np.broadcast_to(scen, (B, scen.shape[1])).copy()
+
+        if rs is not None:
+            rs = self._restrictionsOf(rs, B)
+            if not rs['count'].any():
+                rs = None      # (no scenario is restricted: the plain launch)
+
+        if rs is None:
+            return self._solveBatch(scen, B, multipliers, mass, r0, r1, r2, guess, warmMu, warmPush, devices, classifyFailures, shift, onFirstPass, None)
+
+        # the rows of limits are the handles' for the duration of this solve: handle k holds those of its slice of the batch (msd_solve_batch_multi's slices)
+        if devices is None:
+            handles = [self.problem]
+        else:
+            first, others = self._handles(devices)
+            handles = [first] + others
+        lo = [(B*k)//len(handles) for k in range(len(handles) + 1)]
+        try:
+            for k, h in enumerate(handles):
+                if lo[k + 1] > lo[k]:
+                    h.speed_restrictions(rs['count'][lo[k]:lo[k + 1]], rs['records'][lo[k]:lo[k + 1]])
+            return self._solveBatch(scen, B, multipliers, mass, r0, r1, r2, guess, warmMu, warmPush, devices, classifyFailures, shift, onFirstPass, rs)
+        finally:
+            for h in handles:
+                h.speed_restrictions(None)
+
+    def _solveBatch(self, scen, B, multipliers, mass, r0, r1, r2, guess, warmMu, warmPush, devices, classifyFailures, shift, onFirstPass, rs):
+        "solveBatch behind the scenario records and the rows of limits."
 
         if guess is not None:
             guess = np.asarray(guess, dtype=float)
@@ -357,18 +469,19 @@ class casadiSolver():
         ST = _device.ST
 
         if self.energyOptimal and classifyFailures:
-            self._classify_failures(scen, st, self._overrides(B, mass, r0, r1, r2))
+            self._classify_failures(scen, st, self._overrides(B, mass, r0, r1, r2), rs)
 
         cost = st[:, ST['OBJ']]*(1.0 if self.energyOptimal else self.scalingFactorObjective)   # ocp.py:361
 
         return dict(z=out['z'], status=st[:, ST['STATUS']].astype(int), iterations=st[:, ST['ITERS']].astype(int), cost=cost,
                     stats=st, kernel_ms=out['kernel_ms'], lam_g=out['lam_g'], scenarios=scen)
 
-    def minimumTime(self, scen, overrides=None):
+    def minimumTime(self, scen, overrides=None, speedRestrictions=None):
         """
         Minimum running times of the scenarios `scen` (rows t0, T, v0^2, vN^2; T is ignored): the time-optimal twin of the problem
         (same track, train, transcription and integrator, energyOptimal=False, ocp.py:146-150) solved on the device, with the
-        scenarios' own rolling stock (`overrides`, rows of _overrides()).  Returns (tmin (B,), ok (B,) bool).
+        scenarios' own rolling stock (`overrides`, rows of _overrides()) and under their own speed limits (`speedRestrictions` as in solveBatch:
+        the twin has the same grid).  Returns (tmin (B,), ok (B,) bool).
         """
 
         twin = self.__dict__.get('_twin')
@@ -391,7 +504,17 @@ class casadiSolver():
             ov = np.array(overrides, dtype=float, copy=True)
             ov[:, _device.OV['OBJ_DEN']] = twin._desc.obj_den
 
-        out = twin.problem.solve_batch(loose, overrides=ov)
+        rs = None
+        if speedRestrictions is not None:
+            rs = self._restrictionsOf(self._restrictions(speedRestrictions), sub.shape[0])
+
+        try:
+            if rs is not None and rs['count'].any():
+                twin.problem.speed_restrictions(rs['count'], rs['records'])
+            out = twin.problem.solve_batch(loose, overrides=ov)
+        finally:
+            if rs is not None:
+                twin.problem.speed_restrictions(None)
         st = out['stats']
         # usable: the twin converged -- or it ended without converging on a feasible point next to its optimum: far down the central path (mu <= 1e-5) or
         # with an optimality error of 1e-4 (its primal point settles long before its multipliers do where both brakes share an active acceleration bound:
@@ -406,7 +529,7 @@ class casadiSolver():
 
         return out['z'][:, -2] - sub[:, 0], ok
 
-    def _classify_failures(self, scen, st, overrides=None):
+    def _classify_failures(self, scen, st, overrides=None, restrictions=None):
         """
         IPOPT ends a solve whose constraints cannot be met in its restoration phase with 'Infeasible_Problem_Detected'
         (ocp.py:362-370 prints that status).  The device's restoration phase (csrc/msd_resto.hpp) reports that status itself when it
@@ -414,7 +537,8 @@ class casadiSolver():
         of the missing time over the intervals open).  The host adds an exact certificate
         for the one infeasibility this problem class knows -- a running time below the minimum: the time-optimal twin of the
         problem is solved for the scenarios that broke down (with their own rolling stock), and those whose minimum running
-        time exceeds their T are marked infeasible.  Everything else keeps its status.
+        time exceeds their T are marked infeasible.  Everything else keeps its status.  The twin solves every scenario under the scenario's own
+        speed limits (`restrictions`: the record of _restrictions for the batch), so a running time that only a restriction makes infeasible is found too.
         """
 
         ST = _device.ST
@@ -425,7 +549,8 @@ class casadiSolver():
             return
 
         sub = scen[failed]
-        tmin, ok = self.minimumTime(sub, None if overrides is None else overrides[failed])
+        tmin, ok = self.minimumTime(sub, None if overrides is None else overrides[failed],
+                                    None if restrictions is None else self._restrictionsOf(restrictions, scen.shape[0], failed))
         short = ok & self._twinConverged & (tmin > (sub[:, 1] - sub[:, 0])*(1 + 1e-8))      # (a verdict of infeasibility needs the minimum itself, not an upper bound of it)
         st[failed[short], ST['STATUS']] = _device.STATUS_INFEASIBLE
 
