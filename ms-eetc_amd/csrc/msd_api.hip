@@ -275,9 +275,14 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
      * primal-dual warm start), the one with it otherwise (the reference's starting point, a primal-only warm start) */
     /* ... and its twin with the early results inside for a begun batch or an iteration budget (the same mechanism as kernel_soc; a follow-up kernel is its own) */
     const bool early = ws.d_done != nullptr || ws.budget > 0;
-    const msd::KernelFn fn = (split && !first_pass) ? pl.kernel2
-                           : plain ? ((ws.use_soc && pl.kernel_soc && (!early || pl.kernel_soc_early)) ? (early ? pl.kernel_soc_early : pl.kernel_soc) : (early ? pl.kernel_early : pl.kernel))
-                                   : (early ? pl.kernel_lsq_early : pl.kernel_lsq);
+    /* ... and the twin also where the problem's integrator is not the one the default kernels of the fused family have compiled in (msd_select.hpp:
+     * first_pass_twin).  No twin in the build: early results fail below; another integrator falls back on the default kernel, which hands every scenario over.
+     * The SOCK kernels choose their integrator at run time: for them only `early` decides, as it always did */
+    const bool twin = first_pass_twin(pl.fused_family, early, P.numSteps, P.numApprox);
+    msd::KernelFn fn = (split && !first_pass) ? pl.kernel2
+                     : plain ? ((ws.use_soc && pl.kernel_soc && (!early || pl.kernel_soc_early)) ? (early ? pl.kernel_soc_early : pl.kernel_soc) : (twin ? pl.kernel_early : pl.kernel))
+                             : (twin ? pl.kernel_lsq_early : pl.kernel_lsq);
+    if (!fn && !early) fn = plain ? pl.kernel : pl.kernel_lsq;
     if (!fn) return fail(MSD_E_UNSUPPORTED, "this build holds no first-pass kernel with the early results inside for the handle's problem");
     if (first_out) *first_out = fn;
     const int cap = (split && !first_pass) ? pl.max_grid2 : plain ? pl.max_grid : pl.max_grid_lsq;

@@ -70,6 +70,9 @@
 #ifndef MSD_PARALLEL_RICCATI
 #define MSD_PARALLEL_RICCATI 1      /* stage-parallel KKT solve (scan over the lanes, msd_scan.hpp); 0: serial sweep on one lane */
 #endif
+#ifndef MSD_RUNTIME_INTEGRATOR
+#define MSD_RUNTIME_INTEGRATOR 0    /* 1: every fused first pass chooses its integrator at run time, as up to round 10 (A/B builds; Solver::FIXED_INTEG) */
+#endif
 
 namespace msd {
 
@@ -316,11 +319,25 @@ template <class T> __device__ __forceinline__ T rk4_b(const DevProb &P, T b, T w
     return b;
 }
 
-/* one shooting interval: tau = t+ - t and b+ (train.py:296-301 joint RK4, :324-344 trapezoidal time) */
-template <class T, bool FM = false> __device__ __forceinline__ void interval_map(const DevProb &P, double b0, double w0, double G, double ds, T &tau, T &bplus)
+/* A value as the optimiser sees one that comes out of a branch: nothing behind this point is contracted with the operation that made it (no instruction is
+ * emitted).  Contraction of a*b + c works within a basic block: where interval_map chooses at run time its results cross the end of a branch, in the
+ * FIXED kernels they would not, and a product at the end of the integrator fused with a sum of the pass behind it rounds differently from every other
+ * kernel (round 11: without this the FIXED kernels moved iteration counts on config 1) */
+__device__ __forceinline__ void uncontracted(double &v)
+{
+#ifndef MSD_HOST_EMULATION
+    asm("" : "+v"(v));
+#endif
+}
+__device__ __forceinline__ void uncontracted(Jet &a) { uncontracted(a.v); uncontracted(a.g0); uncontracted(a.g1); uncontracted(a.h00); uncontracted(a.h01); uncontracted(a.h11); }
+
+/* one shooting interval: tau = t+ - t and b+ (train.py:296-301 joint RK4, :324-344 trapezoidal time).  FIXED: the integrator of the first branch is the
+ * only one compiled in -- the default first passes of the fused family (Solver::FIXED_INTEG), which the launch code gives only problems with that
+ * integrator (msd_select.hpp: first_pass_twin) and which hand over any other (Solver::run) */
+template <class T, bool FM = false, bool FIXED = false> __device__ __forceinline__ void interval_map(const DevProb &P, double b0, double w0, double G, double ds, T &tau, T &bplus)
 {
     T b = make_var(T(), b0, 0), w = make_var(T(), w0, 1);
-    if (P.numApprox == 1 && P.numSteps == 1) {
+    if (FIXED || (P.numApprox == 1 && P.numSteps == 1)) {
         /* the integrator of simulations/config.json (one RK4 step, one trapezoid: every BASELINE config), straight-line */
         T k1 = ode_b<T, FM>(P, b, w, G, ds);
         T k2 = ode_b<T, FM>(P, b + k1*0.5, w, G, ds);
@@ -329,6 +346,7 @@ template <class T, bool FM = false> __device__ __forceinline__ void interval_map
         T cur = b + ((k1 + k2*2.0) + (k3*2.0 + k4))*(1.0/6);
         tau = xrecip<FM>(xsqrt<FM>(b) + xsqrt<FM>(cur))*(2*ds*(1.0 - 0.0));
         bplus = cur;
+        if constexpr (FIXED) { uncontracted(tau); uncontracted(bplus); }
         return;
     }
     if (P.numApprox == 0) {
@@ -1963,7 +1981,7 @@ enum { MODE_NEWTON = 0, MODE_LSQ = 1, MODE_RESTO = 2 };      /* (MODE_RESTO: New
 
 /* PART: which part of a solve the enclosing kernel holds (solve_kernel) -- 0 everything, 1 the first pass (no restoration phase), 2 the follow-up,
  * 3 the first pass with the least-squares multiplier estimate in front (any starting point) */
-template <int NT, int SPT, int DYN, bool STREAM, bool GEN, int FULL, int PART = 0, bool SLDS = false, bool SOCK = false>
+template <int NT, int SPT, int DYN, bool STREAM, bool GEN, int FULL, int PART = 0, bool SLDS = false, bool SOCK = false, bool EARLY = false>
 struct Solver {
     static constexpr int S_STRIDE = stage_stride(DYN);
     static constexpr int NS = NT*SPT;      /* node slots of the workgroup */
@@ -3208,7 +3226,7 @@ struct Solver {
                 const double t1 = c.xt[i + 1], b1 = c.xb[i + 1], sb = c.xs[i], sb1 = c.xs[i + 1];
                 const double q = (i > 0) ? c.xf[i - 1] : 0.0;
                 Jet tau, bp;
-                interval_map<Jet, true>(P, b, f + p, nd.G, nd.ds, tau, bp);
+                interval_map<Jet, true, FIXED_INTEG>(P, b, f + p, nd.G, nd.ds, tau, bp);
                 double cv0_ = t1 - (t + tau.v), cv1_ = b1 - bp.v;
                 if constexpr (SOCK) { if (soc) { cv0_ = wf(W_RESC, i); cv1_ = wf(W_RESC + 1, i); } }      /* (second-order correction: the accumulated residuals, merit_fast) */
                 const double cv0 = cv0_, cv1 = cv1_;
@@ -3518,7 +3536,7 @@ struct Solver {
                 const double t = xt[j][VT], b = xt[j][VB], f = xt[j][VF], p = withPn() ? xt[j][VP] : 0.0, s = xt[j][VS];
                 const double t1 = c.xt[i + 1], b1 = c.xb[i + 1], sb = c.xs[i], sb1 = c.xs[i + 1];
                 double tau, bp;
-                interval_map<double, true>(P, b, f + p, nd.G, nd.ds, tau, bp);
+                interval_map<double, true, FIXED_INTEG>(P, b, f + p, nd.G, nd.ds, tau, bp);
                 th += nd.sct*fabs(t1 - (t + tau)) + nd.scb*fabs(b1 - bp);
                 double dv[NR];
                 dv[RPW0] = U.rs[RPW0]*f*sb; dv[RPW1] = U.rs[RPW1]*f*sb1;
@@ -3657,6 +3675,13 @@ struct Solver {
 #define MSD_RESTO 1      /* 0: kernels without the restoration phase (A/B builds) */
 #endif
     static constexpr bool FIRST = PART == 1 || PART == 3;
+    /* Round 11: the default first passes of the fused family hold one integrator, one RK4 step and one trapezoid (numSteps = 1, numApprox = 1: every BASELINE
+     * config) -- the other two branches of interval_map were a fifth of the loop's code and never ran.  The launch code gives a problem with another integrator
+     * the twin (EARLY: solve_kernel_early), which keeps the run-time choice; a scenario that reaches a FIXED_INTEG kernel all the same is handed over (run(),
+     * reason 0) */
+    /* (not the SOCK instantiations: with the integrator fixed their solves moved in the last bits against round 10 on configs 3 and 4, uncontracted() or not --
+     * the cause was not found, so they keep the run-time choice and round 10's instructions) */
+    static constexpr bool FIXED_INTEG = FAST && FIRST && !EARLY && !SOCK && !MSD_RUNTIME_INTEGRATOR;
     /* Every family has the phase (round 5: also the dynamic loss table and integrateLosses -- assemble(MODE_RESTO) leaves their couplings with b_{i+1} resp.
      * the running time unfolded and riccati_resto carries them as cross terms, like the oracle's compute_direction).  Where it lives: in the follow-up
      * kernels.  The kernels with the structure of the reference's rolling stock compiled in have LDS-resident follow-up kernels of their own; every other
@@ -3773,6 +3798,10 @@ struct Solver {
         if constexpr (FL && STRUCT_MASKS) {
             /* the data fix a variable that the structure has free: no fused start for this scenario (reason 0) */
             if (block_any(!structural_start(), c)) { why_general = 0; iters_out = 0; return STATUS_GENERAL; }
+        }
+        if constexpr (FL && FIXED_INTEG) {
+            /* another integrator than the one compiled in (the launch code takes the twin for such a problem): no fused start here either */
+            if (!(P.numSteps == 1 && P.numApprox == 1)) { why_general = 0; iters_out = 0; return STATUS_GENERAL; }
         }
         double mu = mu_start, tau = fmax(K_TAU_MIN, 1 - mu);
         if (!(RESUMABLE && !FL && resume)) {
@@ -4558,7 +4587,7 @@ __device__ __forceinline__ void solve_body(const DevProb &P, int nscen, const do
     }
     c.xb = c.xt + NS; c.xf = c.xb + NS;
     c.o1 = c.xf + NS; c.o2 = c.o1 + NS; c.o3 = c.o2 + NS;
-    using SolverT = Solver<NT, SPT, DYN, STREAM, GEN, FULL, PART, SLDS, SOCK>;
+    using SolverT = Solver<NT, SPT, DYN, STREAM, GEN, FULL, PART, SLDS, SOCK, EARLY>;
     constexpr bool FASTK = SolverT::FAST;
 #ifndef MSD_EARLY_IN_DEFAULT
 #define MSD_EARLY_IN_DEFAULT 0      /* 1: the default instantiations hold the early results too (round 7's kernels; A/B builds) */

@@ -67,6 +67,20 @@ inline void fill_problem(msd::DevProb &P, const msd_problem_desc *d)
     if (d->integrator == MSD_INTEGRATOR_ADAPTIVE) P.numApprox = 0;      /* train.py:314 */
 }
 
+/*
+ * Which first pass of a split launch runs: the default instantiation, or its twin (msd::Geometry::early).  The default first passes of the fused family hold
+ * one integrator -- one RK4 step and one trapezoid per interval (numSteps = 1, numApprox = 1: msd_kernel.hpp, Solver::FIXED_INTEG) -- and no early results; the
+ * twin holds the early results and chooses the integrator at run time.  So the twin runs for a begun batch or an iteration budget (`early`), and on the fused
+ * family for every other integrator shape.  Elsewhere a kernel is its own twin; so is, for the integrator, a first pass with the second-order correction inside
+ * (SOCK), which chooses at run time too: the launch code asks this rule for the kernels without it only.  A default kernel that meets another integrator all the same hands every
+ * scenario to the follow-up kernel (reason 0), which is what a launch falls back on where the build holds no twin and the results are not early ones.
+ */
+inline bool compiled_integrator(int num_steps, int num_approx) { return num_steps == 1 && num_approx == 1; }
+inline bool first_pass_twin(bool fused_family, bool early, int num_steps, int num_approx)
+{
+    return early || (fused_family && !compiled_integrator(num_steps, num_approx));
+}
+
 /* tuning switches of the ladder, set through msd_tuning() of include/mseetc_aux.h (A/B runs, one GPU test): the library reads no environment variable.
  * no_full: the kernels without the structure of the NLP compiled in; two_nodes_per_lane: the 64 x 2 geometry for 65 ... 128 nodes of the loss-table,
  * shooting-integrator and integrateLosses families (default there: 128 x 1) */
