@@ -65,6 +65,44 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
                 double *log, double *z_log, float *loop_ms);
 int msd_mpc_nz(msd_mpc_handle m, int k);
 
+/*
+ * Speed restrictions inside the loop: restrictions per scenario that become known while the train is under way (a temporary speed restriction announced at
+ * re-solve k, a signal aspect, engineering works) -- msd_problem_speed_restrictions (mseetc_hip.h) for the loop, on the loop's own grids.
+ *
+ * A record is (begin [m], end [m], velocity [m/s], first_resolve).  Positions are route coordinates: 0 is the first node of the grid of re-solve 0.
+ * first_resolve is the (integer-valued) index of the re-solve from which the restriction is known; 0: from the start.  Re-solve k starts at origin[k], the route
+ * coordinate of the first node of grid k.  A record counts for its scenario in re-solve k if first_resolve <= k and, with begin_k = begin - origin[k] and
+ * end_k = end - origin[k] (one rounded subtraction each), it restricts at least one interval of grid k under the rule of mseetc_hip.h
+ * (pos[i] < end_k && pos[i+1] > begin_k, pos the node positions of grid k).  A restriction that lies wholly behind the train by then is ignored; that is no error.
+ * The row of limits of scenario s in re-solve k is the row of mseetc_hip.h on grid k from (begin_k, end_k, velocity) of the records that count; the measured speed
+ * is clipped to min(vlim_first[k], velocity of the records that restrict interval 0), the terminal speed to min(terminal_velocity, velocity of the records that
+ * restrict the last interval) -- per scenario, on the device.  These are the rules of mseetc/ocp.py: _scenarios and restrictedLimits under restrictions, bit for
+ * bit (mseetc/mpc.py: DeviceLoop.restrictedLimits is the host statement).
+ *
+ *   origin  [K]                                               non-decreasing, origin[0] = 0
+ *   count   [nscen]                                           records of scenario s, 0 ... max_per_scenario
+ *   records [nscen][max_per_scenario][MSD_MPC_RS_COUNT]       host; entries behind a scenario's count are ignored
+ *
+ * The records are state of the loop: every msd_mpc_run with exactly nscen scenarios runs under them until they are cleared with nscen = 0 (the other arguments may
+ * be NULL then); a run with another nscen returns MSD_E_INVALID and enqueues nothing.  The call waits for the loop's stream and uploads records and counts once;
+ * per re-solve one kernel in front of the scenario records builds the [nscen][N_k+1] rows and the two speed caps, and every launch of the re-solve -- the main one,
+ * the time-optimal twin's, the repeated solves of moved arrival times -- runs under the rows.  Nothing is waited for and nothing crosses PCIe inside the loop.
+ * Without records the loop launches exactly what it launched before this entry point existed.
+ *
+ * MSD_E_INVALID (text in msd_last_error(); the records the loop held stay as they were): a null pointer; max_per_scenario outside 1 ... MSD_RS_MAX; a count outside
+ * 0 ... max_per_scenario; a record that is not finite; end <= begin; velocity <= 0 or velocity^2 <= vmin^2; a first_resolve that is not an integer in 0 ... K-1;
+ * a record that restricts no interval of grid 0; an origin that is not non-decreasing from 0.
+ * Not built: a restriction that is lifted again, end points as grid nodes, a limit equal to the minimum speed.
+ */
+#define MSD_MPC_RS_COUNT 4      /* begin [m], end [m], velocity [m/s], first_resolve */
+int msd_mpc_speed_restrictions(msd_mpc_handle m, const double *origin, int nscen, int max_per_scenario, const int *count, const double *records);
+
+/*
+ * Measurement aid: the rows of re-solve k under the loop's records, built by the kernel the loop launches, rows[nscen][N_k+1] (host).  Waits for the loop's stream.
+ * MSD_E_INVALID when the loop holds no records or k is outside 0 ... K-1.  (tests/test_mpc_speed_restrictions_gpu.py: bit for bit the host statement)
+ */
+int msd_mpc_limit_rows(msd_mpc_handle m, int k, double *rows);
+
 #ifdef __cplusplus
 }
 #endif

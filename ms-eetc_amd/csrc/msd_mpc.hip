@@ -10,6 +10,8 @@
  * growing margins; what the twin does not declare late is on the first of these lists too, arrival time unchanged, and gets both attempts
  * there) -> log -> measured state for the next re-solve.  Every launch is unconditional; the
  * kernels launched on an empty list return at once.
+ * Under speed restrictions (msd_mpc_speed_restrictions) one more kernel in front of the scenario records builds the re-solve's rows of limits and the caps of the
+ * end speeds from the records known by then; every launch of the re-solve, the twin's included, runs under the rows.
  */
 #include <hip/hip_runtime.h>
 
@@ -35,15 +37,72 @@ __global__ void mpc_begin(int B, const double *T_in, double t0, double v0, doubl
 }
 
 /* scenario records (t0, T, v0^2, vN^2) with the clipping of ocp.py:343-344 (mseetc/ocp.py: _scenarios), log of the measured state */
-__global__ void mpc_scen(int B, const double *T, const double *tnow, const double *vnow, double vmin, double vlim0, double vNsq, double *scen, double *log)
+__device__ __forceinline__ void scen_record(int s, const double *T, const double *tnow, const double *vnow, double vmin, double vlim0, double vNsq, double *scen, double *log)
 {
-    const int s = blockIdx.x*blockDim.x + threadIdx.x;
-    if (s >= B) return;
     const double v0 = fmin(fmax(vnow[s], vmin), vlim0);
     double *q = scen + (size_t)MSD_SC_COUNT*s;
     q[MSD_SC_T0] = tnow[s]; q[MSD_SC_TEND] = T[s]; q[MSD_SC_V0SQ] = v0*v0; q[MSD_SC_VNSQ] = vNsq;
     double *l = log + (size_t)MSD_MPC_COUNT*s;
     l[MSD_MPC_T0] = tnow[s]; l[MSD_MPC_V0] = vnow[s]; l[MSD_MPC_RELAXED] = 0.0;
+}
+
+__global__ void mpc_scen(int B, const double *T, const double *tnow, const double *vnow, double vmin, double vlim0, double vNsq, double *scen, double *log)
+{
+    const int s = blockIdx.x*blockDim.x + threadIdx.x;
+    if (s >= B) return;
+    scen_record(s, T, tnow, vnow, vmin, vlim0, vNsq, scen, log);
+}
+
+/* ... under speed restrictions (msd_mpc_speed_restrictions): the end speeds clipped per scenario to the caps mpc_limit_rows wrote, caps[2 s] for the measured speed
+ * (the restricted limit of the first interval), caps[2 s + 1] for the terminal speed (that of the last interval) */
+__global__ void mpc_scen_caps(int B, const double *T, const double *tnow, const double *vnow, double vmin, const double *caps, double *scen, double *log)
+{
+    const int s = blockIdx.x*blockDim.x + threadIdx.x;
+    if (s >= B) return;
+    const double vN = caps[2*s + 1];
+    scen_record(s, T, tnow, vnow, vmin, caps[2*s], __dmul_rn(vN, vN), scen, log);
+}
+
+/*
+ * Rows of speed limits of re-solve k and the two speed caps per scenario from the loop's restriction records (the rule of include/mseetc_mpc.h: limit_rows_kernel of
+ * msd_api.hip on grid k, for the records known by re-solve k, moved into the coordinates of the grid by one rounded subtraction each).  The geometry is that
+ * kernel's: one workgroup per scenario, threads strided over the nodes; the scenario's records are the same for every thread (scalar loads), the row is stored
+ * coalesced.  v*v is one rounded product, the host rule's (mseetc/ocp.py: restrictedLimits).  A record that lies behind the train restricts no interval.
+ *   records [nscen][max_per][MSD_MPC_RS_COUNT], count [nscen], bmax / pos [N+1] of grid k, rows [nscen][N+1], caps [nscen][2]
+ */
+__global__ void __launch_bounds__(256) mpc_limit_rows(int N, int max_per, int k, double origin, const double *bmax, const double *pos, const double *records, const int *count,
+                                                      double vlim0, double vN, double *rows, double *caps)
+{
+    const int s = blockIdx.x;
+    const int n = count[s];
+    const double *rec = records + (size_t)MSD_MPC_RS_COUNT*max_per*s;
+    double *row = rows + (size_t)(N + 1)*s;
+    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
+        double b = bmax[i];
+        if (i >= 1 && i < N) {
+            const double p0 = pos[i - 1], p1 = pos[i], p2 = pos[i + 1];
+            for (int j = 0; j < n; j++) {
+                const double *r = rec + MSD_MPC_RS_COUNT*j;
+                if (r[3] > (double)k) continue;      /* (not announced yet) */
+                const double begin = __dsub_rn(r[0], origin), end = __dsub_rn(r[1], origin), v = r[2];
+                /* interval i-1 or interval i is restricted */
+                if ((p0 < end && p1 > begin) || (p1 < end && p2 > begin)) b = fmin(b, __dmul_rn(v, v));
+            }
+        }
+        row[i] = b;
+    }
+    if (threadIdx.x == 0) {
+        double first = vlim0, last = vN;
+        const double a0 = pos[0], a1 = pos[1], z0 = pos[N - 1], z1 = pos[N];
+        for (int j = 0; j < n; j++) {
+            const double *r = rec + MSD_MPC_RS_COUNT*j;
+            if (r[3] > (double)k) continue;
+            const double begin = __dsub_rn(r[0], origin), end = __dsub_rn(r[1], origin), v = r[2];
+            if (a0 < end && a1 > begin) first = fmin(first, v);
+            if (z0 < end && z1 > begin) last = fmin(last, v);
+        }
+        caps[2*s] = first; caps[2*s + 1] = last;
+    }
 }
 
 /* failed re-solves: into the list of the twin's launch, with a running time the twin can certainly meet (mseetc/ocp.py: minimumTime) */
@@ -152,7 +211,24 @@ struct msd_mpc {
     int cap = 0;
     int nz_max = 0, nz_tw_max = 0, nodes_max = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
+    /* speed restrictions (msd_mpc_speed_restrictions): the records as uploaded (counts behind them), the rows and caps of the re-solve under way; rs_nscen scenarios
+     * have records (0: none) and only a run of exactly that many is accepted */
+    double *d_rs = nullptr, *d_rows = nullptr, *d_caps = nullptr;
+    size_t cap_rs = 0, cap_rows = 0;      /* bytes of d_rs, scenarios of d_rows / d_caps */
+    int rs_nscen = 0, rs_max = 0;
+    std::vector<double> origin;           /* [K] route coordinate of the first node of grid k */
+    double last0 = 0;                     /* position of the last node of grid 0 (the checks of the records) */
 };
+
+/* the rows and caps of re-solve k under the loop's records, on `st` */
+static void launch_rows(msd_mpc *m, int k, hipStream_t st)
+{
+    const msd_host::Plan &pl = m->pl[k];
+    const int N = pl.P.N;
+    const size_t rec_doubles = (size_t)MSD_MPC_RS_COUNT*m->rs_max*m->rs_nscen;
+    hipLaunchKernelGGL(mpc_limit_rows, dim3(m->rs_nscen), dim3(N + 1 < 256 ? 64*((N + 64)/64) : 256), 0, st, N, m->rs_max, k, m->origin[k], pl.P.bmax, pl.P.pos,
+                       (const double *)m->d_rs, (const int *)(m->d_rs + rec_doubles), m->vlim0[k], m->vN, m->d_rows, m->d_caps);
+}
 
 extern "C" {
 
@@ -162,6 +238,7 @@ int msd_mpc_destroy(msd_mpc_handle m)
     if (m->h) { hipSetDevice(m->h->device); hipStreamSynchronize(m->h->stream); m->h->attached_loops--; }
     if (m->twin) m->twin->attached_loops--;
     hipFree(m->d_prof); hipFree(m->d_work); hipFree(m->d_tables); hipFree(m->d_ints); hipFree(m->d_buf); hipFree(m->d_zlog);
+    hipFree(m->d_rs); hipFree(m->d_rows);
     if (m->e0) hipEventDestroy(m->e0);
     if (m->e1) hipEventDestroy(m->e1);
     delete m;
@@ -218,6 +295,7 @@ int msd_mpc_create(msd_handle h, msd_handle twin, const msd_mpc_plan *plan, msd_
     for (int k = 0; k < m->K; k++) {
         const msd_problem_desc *d = plan->problems + k;
         msd_host::pack_profile(d, stage.data() + off);
+        if (k == 0) m->last0 = stage[off + msd_host::profile_doubles(d->num_intervals) - 1];
         msd_host::point_profile(m->pl[k].P, m->d_prof + off);
         if (twin) msd_host::point_profile(m->tw[k].P, m->d_prof + off);
         off += msd_host::profile_doubles(d->num_intervals);
@@ -295,6 +373,10 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
 {
     if (!m || nscen < 1 || !T || (m->K > 1 && m->noise != 0 && (!n1 || !n2))) return fail(MSD_E_INVALID, "bad argument");
     if (!(initial_time >= 0)) return fail(MSD_E_INVALID, "Initial time must be a positive number!");
+    const bool rs = m->rs_nscen != 0;
+    if (rs && nscen != m->rs_nscen)
+        return fail(MSD_E_INVALID, "the loop holds the speed restrictions of " + std::to_string(m->rs_nscen) + " scenarios, the run has " + std::to_string(nscen)
+                                   + " (msd_mpc_speed_restrictions with nscen = 0 clears them)");
     for (int s = 0; s < nscen; s++) if (!(T[s] > 0)) return fail(MSD_E_INVALID, "Terminal time must be a strictly positive number!");
     msd_problem *h = m->h;
     if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
@@ -322,8 +404,14 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
         const msd_host::Plan &pl = m->pl[k];
         const int N = pl.P.N, stp = 4 + pl.P.withPn;
         double *logk = m->d_log + (size_t)MSD_MPC_COUNT*B*k;
-        hipLaunchKernelGGL(mpc_scen, gb, tb, 0, st, B, m->d_T, m->d_tnow, m->d_vnow, m->vmin, m->vlim0[k], m->vN*m->vN, m->d_scen, logk);
+        if (rs) {
+            /* the rows of this grid and the caps of the end speeds from the records known by now, then the scenario records under the caps */
+            launch_rows(m, k, st);
+            hipLaunchKernelGGL(mpc_scen_caps, gb, tb, 0, st, B, m->d_T, m->d_tnow, m->d_vnow, m->vmin, m->d_caps, m->d_scen, logk);
+        } else
+            hipLaunchKernelGGL(mpc_scen, gb, tb, 0, st, B, m->d_T, m->d_tnow, m->d_vnow, m->vmin, m->vlim0[k], m->vN*m->vN, m->d_scen, logk);
         msd_host::WarmStart ws;
+        ws.d_limits = rs ? m->d_rows : nullptr;      /* (every launch of the re-solve: the lists carry original scenario indices, so row s stays with scenario s) */
         const int prev = 1 - cur;
         if (m->warm && k > 0 && m->tail[k]) {
             /* the new grid is the tail of the old one: primal point and multipliers of the previous solutions, `stride` intervals down the horizon */
@@ -339,7 +427,9 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
         if (m->relax) {
             const msd_host::Plan &tw = m->tw[k];
             hipLaunchKernelGGL(mpc_collect, gb, tb, 0, st, B, m->d_st[cur], m->d_scen, 3*m->length[k]/m->vmax, m->d_flag, m->d_listA, m->d_scen_tw);
-            rc = msd_host::launch_plan(tw, st, m->d_work, m->d_follow_tw, queue(), B, m->d_scen_tw, nullptr, m->d_ztw, nullptr, m->d_sttw, nullptr, 0, msd_host::WarmStart(), m->d_listA);
+            msd_host::WarmStart wtw;
+            wtw.d_limits = ws.d_limits;
+            rc = msd_host::launch_plan(tw, st, m->d_work, m->d_follow_tw, queue(), B, m->d_scen_tw, nullptr, m->d_ztw, nullptr, m->d_sttw, nullptr, 0, wtw, m->d_listA);
             if (rc != MSD_OK) { hipStreamSynchronize(st); return rc; }
             double margin = m->margin;
             for (int a = 0; a < 3; a++, margin *= 4) {
@@ -347,6 +437,7 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
                 msd_host::WarmStart cold;
                 cold.d_dual_out = ws.d_dual_out;
                 cold.use_soc = true;
+                cold.d_limits = ws.d_limits;
                 rc = msd_host::launch_plan(pl, st, m->d_work, m->d_follow, queue(), B, m->d_scen, nullptr, m->d_z[cur], nullptr, m->d_st[cur], nullptr, 0, cold, m->d_listB);
                 if (rc != MSD_OK) { hipStreamSynchronize(st); return rc; }
             }
@@ -367,6 +458,73 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
     if (z_log) HIP_TRY(hipMemcpyAsync(z_log, m->d_zlog, sizeof(double)*zoff, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (loop_ms) HIP_TRY(hipEventElapsedTime(loop_ms, m->e0, m->e1));
+    return MSD_OK;
+}
+
+int msd_mpc_speed_restrictions(msd_mpc_handle m, const double *origin, int nscen, int max_per_scenario, const int *count, const double *records)
+{
+    if (!m) return fail(MSD_E_INVALID, "null handle");
+    if (nscen == 0) { m->rs_nscen = 0; return MSD_OK; }      /* (the buffers stay; no run is in flight: msd_mpc_run waits for its own end) */
+    if (nscen < 0 || !origin || !count || !records) return fail(MSD_E_INVALID, "msd_mpc_speed_restrictions: bad argument");
+    if (max_per_scenario < 1 || max_per_scenario > MSD_RS_MAX)
+        return fail(MSD_E_INVALID, "msd_mpc_speed_restrictions: max_per_scenario must be 1 ... " + std::to_string(MSD_RS_MAX));
+    const int K = m->K;
+    for (int k = 0; k < K; k++)
+        if (!std::isfinite(origin[k]) || (k == 0 ? origin[0] != 0 : origin[k] < origin[k - 1]))
+            return fail(MSD_E_INVALID, "msd_mpc_speed_restrictions: origin must be non-decreasing from 0");
+    const double vminSq = m->pl[0].P.vminSq;
+    for (int s = 0; s < nscen; s++) {
+        const auto bad = [&](int j, const char *what) {
+            return fail(MSD_E_INVALID, "speed restriction " + std::to_string(j) + " of scenario " + std::to_string(s) + " " + what);
+        };
+        if (count[s] < 0 || count[s] > max_per_scenario) return fail(MSD_E_INVALID, "scenario " + std::to_string(s) + ": the number of speed restrictions must be 0 ... max_per_scenario");
+        for (int j = 0; j < count[s]; j++) {
+            const double *r = records + (size_t)MSD_MPC_RS_COUNT*((size_t)max_per_scenario*s + j);
+            const double begin = r[0], end = r[1], v = r[2], first = r[3];
+            if (!std::isfinite(begin) || !std::isfinite(end) || !std::isfinite(v) || !std::isfinite(first)) return bad(j, "is not finite");
+            if (!(end > begin)) return bad(j, "ends at or before its beginning");
+            if (!(v > 0) || !(v*v > vminSq)) return bad(j, "is not above the minimum speed (a limit equal to it fixes adjacent nodes: not supported)");
+            if (first != std::floor(first) || first < 0 || first > K - 1) return bad(j, "is not known from a re-solve 0 ... K-1 (first_resolve)");
+            /* some interval of grid 0 is restricted  <=>  the restriction overlaps (pos[0], pos[N]) = (0, last0): the nodes are increasing */
+            if (!(end > 0 && begin < m->last0)) return bad(j, "restricts no interval of the grid of re-solve 0");
+        }
+    }
+    msd_problem *h = m->h;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    m->rs_nscen = 0;      /* (until the upload has ended: a HIP failure below leaves the loop without records, not with half of them) */
+    const size_t rec_doubles = (size_t)MSD_MPC_RS_COUNT*max_per_scenario*nscen;
+    const size_t rec_bytes = sizeof(double)*rec_doubles + sizeof(int)*(size_t)nscen;      /* records, then the counts */
+    if (rec_bytes > m->cap_rs) {
+        hipFree(m->d_rs); m->d_rs = nullptr; m->cap_rs = 0;
+        HIP_TRY(hipMalloc((void **)&m->d_rs, rec_bytes));
+        m->cap_rs = rec_bytes;
+    }
+    if ((size_t)nscen > m->cap_rows) {
+        /* the rows of one re-solve at a time, for the longest grid, and the two caps per scenario behind them */
+        hipFree(m->d_rows); m->d_rows = nullptr; m->d_caps = nullptr; m->cap_rows = 0;
+        HIP_TRY(hipMalloc((void **)&m->d_rows, sizeof(double)*((size_t)m->nodes_max + 2)*nscen));
+        m->cap_rows = nscen;
+    }
+    m->d_caps = m->d_rows + (size_t)m->nodes_max*m->cap_rows;
+    HIP_TRY(hipMemcpy(m->d_rs, records, sizeof(double)*rec_doubles, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_rs + rec_doubles, count, sizeof(int)*(size_t)nscen, hipMemcpyHostToDevice));
+    m->origin.assign(origin, origin + K);
+    m->rs_nscen = nscen; m->rs_max = max_per_scenario;
+    return MSD_OK;
+}
+
+int msd_mpc_limit_rows(msd_mpc_handle m, int k, double *rows)
+{
+    if (!m || !rows) return fail(MSD_E_INVALID, "bad argument");
+    if (!m->rs_nscen) return fail(MSD_E_INVALID, "the loop holds no speed restrictions (msd_mpc_speed_restrictions)");
+    if (k < 0 || k >= m->K) return fail(MSD_E_INVALID, "msd_mpc_limit_rows: re-solve outside 0 ... K-1");
+    msd_problem *h = m->h;
+    HIP_TRY(hipSetDevice(h->device));
+    launch_rows(m, k, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rows, m->d_rows, sizeof(double)*(size_t)(m->pl[k].P.N + 1)*m->rs_nscen, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MSD_OK;
 }
 

@@ -63,6 +63,7 @@ class MpcPlan(ctypes.Structure):
 
 
 MPC = dict(T0=0, V0=1, T=2, STATUS=3, ITERS=4, OBJ=5, RELAXED=6, COUNT=7)      # MSD_MPC_*
+MPC_RS_COUNT = 4      # MSD_MPC_RS_COUNT: (begin [m], end [m], velocity [m/s], first_resolve) of a speed restriction inside the loop
 
 
 class DeviceError(RuntimeError):
@@ -141,6 +142,8 @@ def lib():
         L.msd_mpc_destroy.argtypes = [vp]
         L.msd_mpc_run.argtypes = [vp, ctypes.c_int, _dptr, ctypes.c_double, ctypes.c_double, _dptr, _dptr, _dptr, _dptr, ctypes.POINTER(ctypes.c_float)]
         L.msd_mpc_nz.argtypes = [vp, ctypes.c_int]
+        L.msd_mpc_speed_restrictions.argtypes = [vp, _dptr, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _dptr]
+        L.msd_mpc_limit_rows.argtypes = [vp, ctypes.c_int, _dptr]
 
         _lib = L
 
@@ -739,6 +742,42 @@ class DeviceLoop():
             for nz in self.nz:
                 zs.append(zflat[off:off + B*nz].reshape(B, nz)); off += B*nz
         return log, zs, float(ms.value)
+
+    def speed_restrictions(self, origin, count=None, records=None):
+        """
+        Speed restrictions inside the loop (msd_mpc_speed_restrictions): origin (K,) route coordinate of the first node of every grid, count (B,) records
+        of every scenario, records (B, M, MPC_RS_COUNT) rows of (begin [m], end [m], velocity [m/s], first_resolve) in route coordinates, M <= RS_MAX.
+        Every run of exactly B scenarios is under them until they are cleared.  count None: clears them.
+        """
+
+        L = lib()
+        if count is None:
+            _check(L.msd_mpc_speed_restrictions(self._m, None, 0, 1, None, None))
+            self._rs = 0
+            return self
+        origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        if origin.shape[0] != self.K:
+            raise ValueError("origin must hold the first position of each of the {} re-solves!".format(self.K))
+        count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        B = count.shape[0]
+        records = np.ascontiguousarray(records, dtype=np.float64)
+        if records.ndim != 3 or records.shape[0] != B or records.shape[2] != MPC_RS_COUNT:
+            raise ValueError("speed restriction records must have shape ({}, M, {})!".format(B, MPC_RS_COUNT))
+        _check(L.msd_mpc_speed_restrictions(self._m, _d(origin), B, int(records.shape[1]), count.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _d(records)))
+        self._rs = B
+        return self
+
+    def limit_rows(self, k, B):
+        "The (B, N_k + 1) rows of limits of re-solve k, built by the kernel the loop launches (msd_mpc_limit_rows: waits for the loop's stream)."
+
+        held = getattr(self, "_rs", 0)
+        if int(B) != held:
+            raise ValueError("the loop holds the speed restrictions of {} scenarios, not of {}!".format(held, int(B)))
+        if not 0 <= int(k) < self.K:
+            raise ValueError("re-solve {} is outside 0 ... {}!".format(k, self.K - 1))
+        rows = np.zeros((int(B), self._descs[int(k)].num_intervals + 1))
+        _check(lib().msd_mpc_limit_rows(self._m, int(k), _d(rows)))
+        return rows
 
     def close(self):
 

@@ -63,6 +63,84 @@ def transferSolution(z, positionsOld, positionsNew, withPnBrake):
     return out
 
 
+def _restrictionSets(speedRestrictions, B, K, velocityMin, positionsFirst):
+    """
+    Speed restrictions of a loop (include/mseetc_mpc.h), validated like casadiSolver._restrictions: a sequence of B sequences of
+    (begin [m], end [m], velocity [m/s][, firstResolve]) in route coordinates (0: the first node of the first grid), or one such sequence for every
+    scenario; firstResolve (default 0) is the re-solve from which the restriction is known.  Returns a list of B lists of 4-tuples of floats.
+    `K` re-solves, `positionsFirst` the nodes of the first grid.
+    """
+
+    from . import _device
+
+    sets = list(speedRestrictions)
+    def record(e):
+        try:
+            return len(e) in (_device.RS_COUNT, _device.MPC_RS_COUNT) and all(np.ndim(x) == 0 for x in e)
+        except TypeError:
+            return False
+
+    def records(one):
+        try:
+            return all(record(e) for e in one)
+        except TypeError:
+            return False
+
+    if all(record(e) for e in sets):      # (one sequence of restrictions -- an empty one too -- for the whole batch)
+        sets = [sets]*B
+    if not all(records(one) for one in sets):
+        raise ValueError("Speed restrictions are given as (begin [m], end [m], velocity [m/s][, firstResolve])!")
+    if len(sets) != B:
+        raise ValueError("{} sets of speed restrictions for a batch of {} scenarios!".format(len(sets), B))
+    if max([len(one) for one in sets], default=0) > _device.RS_MAX:
+        raise ValueError("At most {} speed restrictions per scenario!".format(_device.RS_MAX))
+
+    pos = np.asarray(positionsFirst, dtype=float)
+    out = []
+    for s, one in enumerate(sets):
+        recs = []
+        for j, rec in enumerate(one):
+            begin, end, velocity = [float(x) for x in rec[:3]]
+            first = float(rec[3]) if len(rec) == _device.MPC_RS_COUNT else 0.0
+            if not np.all(np.isfinite([begin, end, velocity, first])):
+                raise ValueError("Speed restriction {} of scenario {} is not finite!".format(j, s))
+            if end <= begin:
+                raise ValueError("Speed restriction {} of scenario {} ends at or before its beginning!".format(j, s))
+            if velocity <= 0 or velocity*velocity <= float(velocityMin)**2:
+                raise ValueError("Speed restriction {} of scenario {} is not above the minimum velocity!".format(j, s))
+            if first != np.floor(first) or not 0 <= first <= K - 1:
+                raise ValueError("Speed restriction {} of scenario {} is not known from a re-solve 0 ... {}!".format(j, s, K - 1))
+            if not ((pos[:-1] < end) & (pos[1:] > begin)).any():
+                raise ValueError("Speed restriction {} of scenario {} restricts no interval of the first grid!".format(j, s))
+            recs.append((begin, end, velocity, first))
+        out.append(recs)
+
+    return out
+
+
+def _restrictionsOfResolve(sets, k, origin, positions):
+    """
+    The restrictions (begin, end, velocity) of re-solve k in the coordinates of its grid, per scenario: the records of _restrictionSets that are known by
+    re-solve k, moved by the route coordinate `origin` of the grid's first node (one rounded subtraction each), without those that restrict no interval
+    of the grid any more (`positions`: its nodes, first one 0) -- a restriction wholly behind the train.  What casadiSolver.solveBatch / restrictedLimits take.
+    """
+
+    pos = np.asarray(positions, dtype=float)
+    origin = float(origin)
+    out = []
+    for one in sets:
+        keep = []
+        for begin, end, velocity, first in one:
+            if first > k:
+                continue
+            b, e = begin - origin, end - origin
+            if ((pos[:-1] < e) & (pos[1:] > b)).any():
+                keep.append((b, e, velocity))
+        out.append(keep)
+
+    return out
+
+
 class DeviceLoop():
     """
     The shrinking-horizon loop with its bookkeeping on the device (csrc/msd_mpc.hip, include/mseetc_mpc.h): the grid sequence does not depend
@@ -72,7 +150,7 @@ class DeviceLoop():
     """
 
     def __init__(self, train, track, optsDict, numResolves, stride=2, noise=0.0, terminalVelocity=1.0, device=0, warmStart=False, warmPush=1e-3,
-                 dualMu=1e-4, relaxInfeasible=True, lateMargin=5e-3):
+                 dualMu=1e-4, relaxInfeasible=True, lateMargin=5e-3, deferDevice=False):
 
         from . import _device
 
@@ -110,24 +188,98 @@ class DeviceLoop():
         self.energyOptimal = first.energyOptimal
         self.scale = 1.0 if first.energyOptimal else first.scalingFactorObjective
         self.withPnBrake = first.withPnBrake
-        self._loop = _device.DeviceLoop(first.problem, self.twins[0].problem if relaxInfeasible else None, [s._desc for s in self.solvers],
-                                        [t._desc for t in self.twins] if relaxInfeasible else None, stride,
-                                        [s.points['Speed limit [m/s]'].values[0] for s in self.solvers], [s.track.length for s in self.solvers], tail,
-                                        first.velocityMin, first._vmaxTrain, min(max(terminalVelocity, first.velocityMin), vlim[-1]), warmStart, dualMu, warmPush,
-                                        noise, relaxInfeasible, lateMargin)
+        self.terminalVelocity = terminalVelocity
+        # everything above is host work, and so are restrictedLimits and restrictedScenarios: with `deferDevice` the device side is created by the first run
+        self._loop = None
+        self._make = lambda: _device.DeviceLoop(first.problem, self.twins[0].problem if relaxInfeasible else None, [s._desc for s in self.solvers],
+                                                [t._desc for t in self.twins] if relaxInfeasible else None, stride,
+                                                [s.points['Speed limit [m/s]'].values[0] for s in self.solvers], [s.track.length for s in self.solvers], tail,
+                                                first.velocityMin, first._vmaxTrain, min(max(terminalVelocity, first.velocityMin), vlim[-1]), warmStart, dualMu,
+                                                warmPush, noise, relaxInfeasible, lateMargin)
+        if not deferDevice:
+            self._loop = self._make()
 
-    def run(self, terminalTime, seed=0, initialTime=0.0, initialVelocity=1.0, keepZ=True):
-        "One loop; returns the log of shrinkingHorizon() (list of dicts per re-solve; 'z' None without keepZ) -- `loop_ms` in every entry is the device time of the whole loop."
+    @property
+    def device(self):
+        "The owner of the loop's device handle (_device.DeviceLoop), created on first use."
 
-        from ._device import MPC
+        if self._loop is None:
+            self._loop = self._make()
+        return self._loop
+
+    # ---- speed restrictions inside the loop (include/mseetc_mpc.h) ------------------------------
+
+    def _restrictionSets(self, speedRestrictions, B):
+        return _restrictionSets(speedRestrictions, B, self.K, self.solvers[0].velocityMin, self.positions[0])
+
+    def _restrictionsOfResolve(self, k, speedRestrictions, B):
+        "The restrictions that count in re-solve k, per scenario, in the coordinates of grid k."
+
+        if not 0 <= int(k) < self.K:
+            raise ValueError("Re-solve {} is outside 0 ... {}!".format(k, self.K - 1))
+        return _restrictionsOfResolve(self._restrictionSets(speedRestrictions, int(B)), int(k), self.positions[k][0], self.solvers[k].points.index.values)
+
+    def restrictionRecords(self, speedRestrictions, B):
+        "(origin (K,), count (B,), records (B, M, 4)): the restrictions as msd_mpc_speed_restrictions takes them (_device.DeviceLoop.speed_restrictions)."
+
+        from ._device import MPC_RS_COUNT
+
+        sets = self._restrictionSets(speedRestrictions, int(B))
+        count = np.array([len(one) for one in sets], dtype=np.int32)
+        records = np.zeros((int(B), max(1, int(count.max(initial=0))), MPC_RS_COUNT))
+        for s, one in enumerate(sets):
+            for j, rec in enumerate(one):
+                records[s, j] = rec
+
+        return np.array([float(p[0]) for p in self.positions]), count, records
+
+    def restrictedLimits(self, k, speedRestrictions, B):
+        """
+        (B, N_k+1) upper bounds of b = v^2 of re-solve k under the loop's speed restrictions (`speedRestrictions` as in run): the numpy statement of the
+        rows the device builds.  The records known by re-solve k, in the coordinates of grid k, without those behind the train; then the rule of
+        casadiSolver.restrictedLimits on that grid.
+        """
+
+        now = self._restrictionsOfResolve(k, speedRestrictions, B)
+
+        return self.solvers[k].restrictedLimits(now, int(B))
+
+    def restrictedScenarios(self, k, terminalTime, initialTime, initialVelocity, speedRestrictions, B):
+        "(B, 4) scenario records (t0, T, v0^2, vN^2) of re-solve k from the measured state: the end speeds clipped to the restricted limits per scenario (casadiSolver._scenarios)."
+
+        now = self._restrictionsOfResolve(k, speedRestrictions, B)
+        solver = self.solvers[k]
+        rs = solver._restrictionsOf(solver._restrictions(now), int(B))
+        scen = solver._scenarios(terminalTime, initialTime, self.terminalVelocity, initialVelocity, rs)
+        return np.broadcast_to(scen, (int(B), scen.shape[1])).copy()
+
+    def run(self, terminalTime, seed=0, initialTime=0.0, initialVelocity=1.0, keepZ=True, speedRestrictions=None):
+        """
+        One loop; returns the log of shrinkingHorizon() (list of dicts per re-solve; 'z' None without keepZ) -- `loop_ms` in every entry is the device time of the whole loop.
+        `speedRestrictions`: a sequence of B sequences of (begin [m], end [m], velocity [m/s][, firstResolve]), or one such sequence for every scenario --
+        restrictions in route coordinates (0: the first node of the first grid) that are known from re-solve `firstResolve` on (default 0): from then on the
+        scenario's re-solves run under restrictedLimits(k, ...), their end speeds clipped to the restricted limits; a restriction the train has passed is
+        ignored.  ValueError: a record that is not finite, ends at or before its beginning, restricts no interval of the first grid, is not above the minimum
+        velocity or names no re-solve of the loop; more than 16 per scenario; a wrong batch length.  The records are the loop's for this run only.
+        """
+
+        from ._device import MPC, MPC_RS_COUNT
 
         T = np.array(np.atleast_1d(np.asarray(terminalTime, dtype=float)), copy=True)
         B = T.shape[0]
+        sets = self._restrictionSets(speedRestrictions, B) if speedRestrictions is not None else None
         rng = np.random.default_rng(seed)
         n1, n2 = np.zeros((max(self.K - 1, 0), B)), np.zeros((max(self.K - 1, 0), B))
         for k in range(self.K - 1):      # (the order of shrinkingHorizon's draws)
             n1[k], n2[k] = rng.standard_normal(B), rng.standard_normal(B)
-        log, zs, ms = self._loop.run(T, initialTime, initialVelocity, n1, n2, keepZ=keepZ)
+        if sets is not None and any(sets):
+            try:
+                self.device.speed_restrictions(*self.restrictionRecords(sets, B))
+                log, zs, ms = self.device.run(T, initialTime, initialVelocity, n1, n2, keepZ=keepZ)
+            finally:
+                self.device.speed_restrictions(None)
+        else:      # (no scenario is restricted: the plain loop)
+            log, zs, ms = self.device.run(T, initialTime, initialVelocity, n1, n2, keepZ=keepZ)
         out = []
         for k in range(self.K):
             r = log[k]
@@ -149,7 +301,8 @@ class DeviceLoop():
 
 def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2, noise=0.0, seed=0,
                      initialTime=0.0, initialVelocity=1.0, terminalVelocity=1.0, device=0, solverFactory=None,
-                     warmStart=False, warmMu=1e-2, warmPush=1e-3, dualMu=1e-4, relaxInfeasible=True, lateMargin=5e-3, onDevice=False):
+                     warmStart=False, warmMu=1e-2, warmPush=1e-3, dualMu=1e-4, relaxInfeasible=True, lateMargin=5e-3, onDevice=False,
+                     speedRestrictions=None):
     """
     Re-solve `numResolves` times; after each solve the train advances `stride` intervals of the current grid, the
     measured time and speed at that node are perturbed by `noise` (relative, standard normal) and the remaining
@@ -167,6 +320,12 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
     terminalTime: array (B,) of arrival times (absolute).
     Returns a list of dicts per re-solve: position [m], numIntervals, t0 (B,), v0 (B,), T (B,), status, iterations, cost, z, relaxed (B,) bool.
     `solverFactory(train, track, opts)` lets tests substitute the solver (default: the device solver).
+
+    `speedRestrictions`: restrictions per scenario that become known while the train is under way -- a sequence of B sequences of
+    (begin [m], end [m], velocity [m/s][, firstResolve]) in route coordinates (0: the start of `track`), or one such sequence for every scenario; as in
+    DeviceLoop.run.  From re-solve `firstResolve` on the scenario is solved under the restriction (casadiSolver.solveBatch(speedRestrictions=...) on the grid
+    of the re-solve), its minimum running time is the one under the restriction, and a restriction the train has passed is ignored.  A substituted solver
+    must accept the keyword `speedRestrictions` in solveBatch.
     """
 
     if onDevice:
@@ -176,7 +335,7 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
         loop = DeviceLoop(train, track, optsDict, numResolves, stride=stride, noise=noise, terminalVelocity=terminalVelocity, device=device, warmStart=warmStart,
                           warmPush=warmPush, dualMu=dualMu, relaxInfeasible=relaxInfeasible, lateMargin=lateMargin)
         try:
-            return loop.run(terminalTime, seed=seed, initialTime=initialTime, initialVelocity=initialVelocity)
+            return loop.run(terminalTime, seed=seed, initialTime=initialTime, initialVelocity=initialVelocity, speedRestrictions=speedRestrictions)
         finally:
             loop.close()
 
@@ -243,6 +402,16 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
 
             common = dict(initialTime=t_now, terminalVelocity=terminalVelocity, initialVelocity=v_now)
 
+            setsNow = None
+            if speedRestrictions is not None:
+                # the restrictions known by now, in the coordinates of this grid, without those behind the train (include/mseetc_mpc.h)
+                if k == 0:
+                    from .ocp import OptionsCasadiSolver
+                    numSolves = sum(1 for j in range(numResolves) if N - stride*j >= 1)
+                    sets = _restrictionSets(speedRestrictions, B, numSolves, OptionsCasadiSolver(optsDict).minimumVelocity, solver.points.index.values)
+                setsNow = _restrictionsOfResolve(sets, k, position + solver.points.index.values[0], solver.points.index.values)
+                common['speedRestrictions'] = setsNow
+
             posNew = position + solver.points.index.values
             tail = (warmStart and previous is not None and batchOnDevice and hasattr(solver, 'adoptDevice') and solverFactory is None and
                     len(previous[1]) - len(posNew) == stride and np.allclose(posNew, previous[1][stride:], rtol=0, atol=1e-6))
@@ -275,8 +444,13 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
             if relaxInfeasible and bad.size and hasattr(solver, 'minimumTime'):
                 # what stops these scenarios is their arrival time: the minimum running time from the measured state (time-optimal twin of
                 # this re-solve's problem) tells, and becomes the new arrival time where it is later than the one asked for
-                scenBad = solver._scenarios(T[bad], t_now[bad], terminalVelocity, v_now[bad])
-                tmin, okMin = solver.minimumTime(scenBad)
+                if setsNow is None:
+                    scenBad = solver._scenarios(T[bad], t_now[bad], terminalVelocity, v_now[bad])
+                    tmin, okMin = solver.minimumTime(scenBad)
+                else:
+                    setsBad = [setsNow[i] for i in bad]
+                    scenBad = solver._scenarios(T[bad], t_now[bad], terminalVelocity, v_now[bad], solver._restrictions(setsBad))
+                    tmin, okMin = solver.minimumTime(scenBad, speedRestrictions=setsBad)
                 late = okMin & (tmin > (T[bad] - t_now[bad]))
                 if late.any():
                     idx, tm = bad[late], tmin[late]
@@ -285,7 +459,8 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
                     for attempt in range(3):
                         # (an interior-point solve needs some room above the minimum running time: a scenario that still breaks down gets four times the margin)
                         T[idx] = t_now[idx] + tm*(1 + margin)
-                        again = solver.solveBatch(T[idx], initialTime=t_now[idx], terminalVelocity=terminalVelocity, initialVelocity=v_now[idx], classifyFailures=False)
+                        under = {} if setsNow is None else dict(speedRestrictions=[setsNow[i] for i in idx])
+                        again = solver.solveBatch(T[idx], initialTime=t_now[idx], terminalVelocity=terminalVelocity, initialVelocity=v_now[idx], classifyFailures=False, **under)
                         for key in ('z', 'status', 'iterations', 'cost'):
                             res[key][idx] = again[key]
                         kernel_extra += float(again.get('kernel_ms', 0.0))
