@@ -91,7 +91,8 @@ int msd_mpc_nz(msd_mpc_handle m, int k);
  *
  * MSD_E_INVALID (text in msd_last_error(); the records the loop held stay as they were): a null pointer; max_per_scenario outside 1 ... MSD_RS_MAX; a count outside
  * 0 ... max_per_scenario; a record that is not finite; end <= begin; velocity <= 0 or velocity^2 <= vmin^2; a first_resolve that is not an integer in 0 ... K-1;
- * a record that restricts no interval of grid 0; an origin that is not non-decreasing from 0.
+ * a record that restricts no interval of grid 0; an origin that is not non-decreasing from 0; an nscen other than that of the rolling stock the loop holds
+ * (msd_mpc_rolling_stock).
  * Not built: a restriction that is lifted again, end points as grid nodes, a limit equal to the minimum speed.
  */
 #define MSD_MPC_RS_COUNT 4      /* begin [m], end [m], velocity [m/s], first_resolve */
@@ -102,6 +103,46 @@ int msd_mpc_speed_restrictions(msd_mpc_handle m, const double *origin, int nscen
  * MSD_E_INVALID when the loop holds no records or k is outside 0 ... K-1.  (tests/test_mpc_speed_restrictions_gpu.py: bit for bit the host statement)
  */
 int msd_mpc_limit_rows(msd_mpc_handle m, int k, double *rows);
+
+/*
+ * Rolling stock inside the loop: a train of its own per scenario for the controller (config 3: msd_solve_batch_ex for the loop) and a plant per scenario -- the
+ * train that actually runs, which need not be the controller's model.
+ *
+ * model [nscen][MSD_OV_COUNT]: the override rows of msd_solve_batch_ex (mseetc_hip.h), with its checks.  Row s goes into the main launch and the repeated solves
+ * of every re-solve of scenario s; the time-optimal twin runs under the same row with MSD_OV_OBJ_DEN replaced by the objective scaling of the twin of that
+ * re-solve (a constant of the twin's problem, length / maximum speed of grid k, not a function of the mass), rewritten on the device per re-solve.  NULL: the
+ * problems' own train.
+ *
+ * plant [nscen][MSD_MPC_PL_COUNT]: without it the state the next re-solve starts from is read from node `stride` of the plan, which makes the plan its own plant.
+ * With it one kernel per advance integrates the plant from the re-solve's own initial state (t0 and the clipped v0^2 of its scenario record) over the first
+ * `stride` intervals of grid k under the planned forces w_i = (Fel_i + Fpb_i) force_scale of the re-solve's solution: per interval the explicit Runge-Kutta map of
+ * the solver (4th order, plant_steps steps per interval, time integrated with the same stages: num_approx_steps = 0) with the plant's specific Davis
+ * coefficients and the problem's own g, rho and track resistance -- whatever shooting integrator or loss model the problems have.  The noise is applied to that
+ * state as it is to the plan's.  After an interval, !(b+ >= vmin^2) or a non-finite running time marks the scenario stalled: it keeps its last measurement from
+ * then on (like a scenario whose re-solve failed) and MSD_MPC_PS_STALLED is 1 in this and every later record.  NULL: the plan is the plant.
+ *
+ * The records are state of the loop exactly like the speed restrictions: uploaded once; every msd_mpc_run with exactly nscen scenarios runs under them;
+ * nscen = 0 clears them (the other arguments are ignored); a run with another count returns MSD_E_INVALID and enqueues nothing; refused records leave the previous
+ * ones in place.  Restrictions and rolling stock compose; where the loop holds both their counts must agree (the later call is refused otherwise).  Nothing is
+ * waited for and nothing crosses PCIe inside the loop.  With neither array the loop launches exactly what it launched before this entry point existed.
+ *
+ * MSD_E_INVALID: nscen < 0; both arrays NULL with nscen > 0; a model row msd_solve_batch_ex refuses; a plant row that is not finite, has a negative Davis
+ * coefficient or force_scale <= 0; plant_steps outside 1 ... 64 (with a plant); a count other than that of the speed restrictions the loop holds.
+ * Not built: a plant rho, adhesion or force limits of its own; a plant for the loss model; disturbance estimation.
+ */
+enum { MSD_MPC_PL_SR0 = 0, MSD_MPC_PL_SR1, MSD_MPC_PL_SR2,   /* specific Davis coefficients of the plant (per kg of ITS mass*rho) */
+       MSD_MPC_PL_FORCE_SCALE,                               /* (mass*rho of the scenario's model) / (mass*rho of the plant): commanded newtons -> plant's specific force */
+       MSD_MPC_PL_COUNT };
+int msd_mpc_rolling_stock(msd_mpc_handle m, int nscen, const double *model, const double *plant, int plant_steps);
+
+/*
+ * The plant's state behind every advance of the last run, before the noise: states[K-1][nscen][MSD_MPC_PS_COUNT] (host), record k for the advance behind re-solve
+ * k.  MSD_MPC_PS_T [s] and MSD_MPC_PS_V [m/s]: the state at node `stride` of grid k; for a scenario that stalls in this advance the last state in front of the
+ * interval that stalled it; for a scenario that was not advanced (its re-solve failed, or it stalled earlier) the measurement it keeps.
+ * MSD_E_INVALID: the loop holds no plant, or has not run under it yet.
+ */
+enum { MSD_MPC_PS_T = 0, MSD_MPC_PS_V, MSD_MPC_PS_STALLED, MSD_MPC_PS_COUNT };
+int msd_mpc_plant_states(msd_mpc_handle m, double *states);
 
 #ifdef __cplusplus
 }

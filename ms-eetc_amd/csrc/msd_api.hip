@@ -319,6 +319,21 @@ int launch_plan(const Plan &pl, hipStream_t stream, double *d_work, int *d_follo
     return MSD_OK;
 }
 
+/* rolling-stock overrides [nscen][MSD_OV_COUNT] of a batch (msd_solve_batch_ex; the model rows of msd_mpc_rolling_stock) */
+int check_overrides(bool fused_family, int nscen, const double *overrides)
+{
+    for (int k = 0; k < nscen; k++) {
+        const double *o = overrides + (size_t)MSD_OV_COUNT*k;
+        if (!(o[MSD_OV_OBJ_DEN] > 0) || !(o[MSD_OV_F_MAX] > o[MSD_OV_F_MIN]) || !(o[MSD_OV_SR0] >= 0) || !(o[MSD_OV_SR1] >= 0) || !(o[MSD_OV_SR2] >= 0) ||
+            !(o[MSD_OV_TOTAL_MASS] >= 0))
+            return fail(MSD_E_INVALID, "invalid rolling-stock override");
+        /* the kernels with the row structure compiled in take both power rows as two-sided (finite by construction in the problem record: ocp.py:186-187) */
+        if (fused_family && (!std::isfinite(o[MSD_OV_PW_UPPER]) || !std::isfinite(o[MSD_OV_PW_LOWER])))
+            return fail(MSD_E_INVALID, "rolling-stock override with an infinite power bound on a problem whose power rows are bounded");
+    }
+    return MSD_OK;
+}
+
 }  // namespace msd_host
 
 using msd_host::check_desc;
@@ -686,16 +701,10 @@ static int check_batch(msd_handle h, int nscen, const double *scen, const double
     if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
     if (z_guess && (!(mu_init > 0) || !(mu_init <= 1e3) || !(bound_push > 0) || !(bound_push <= 0.5)))
         return fail(MSD_E_INVALID, "warm start needs 0 < mu_init <= 1e3 and 0 < bound_push <= 0.5");
-    if (overrides)
-        for (int k = 0; k < nscen; k++) {
-            const double *o = overrides + (size_t)MSD_OV_COUNT*k;
-            if (!(o[MSD_OV_OBJ_DEN] > 0) || !(o[MSD_OV_F_MAX] > o[MSD_OV_F_MIN]) || !(o[MSD_OV_SR0] >= 0) || !(o[MSD_OV_SR1] >= 0) || !(o[MSD_OV_SR2] >= 0) ||
-                !(o[MSD_OV_TOTAL_MASS] >= 0))
-                return fail(MSD_E_INVALID, "invalid rolling-stock override");
-            /* the kernels with the row structure compiled in take both power rows as two-sided (finite by construction in the problem record: ocp.py:186-187) */
-            if (h->plan.fused_family && (!std::isfinite(o[MSD_OV_PW_UPPER]) || !std::isfinite(o[MSD_OV_PW_LOWER])))
-                return fail(MSD_E_INVALID, "rolling-stock override with an infinite power bound on a problem whose power rows are bounded");
-        }
+    if (overrides) {
+        const int rc = msd_host::check_overrides(h->plan.fused_family, nscen, overrides);
+        if (rc != MSD_OK) return rc;
+    }
     for (int k = 0; k < nscen; k++) {
         const double *s = scen + (size_t)MSD_SC_COUNT*k;
         if (!(s[MSD_SC_T0] >= 0)) return fail(MSD_E_INVALID, "Initial time must be a positive number!");

@@ -55,6 +55,7 @@ int make_plan(int device, const msd_problem_desc *d, Plan *out);               /
  * kernel2 and `soc` ("-": none, "?": a pointer that is no exported symbol) -- msd_plan_describe and the MSD_DEBUG_PTRS print of the diagnostic builds */
 std::string plan_text(const Plan &pl, msd::KernelFn soc);
 
+int check_overrides(bool fused_family, int nscen, const double *overrides);      /* the checks of msd_solve_batch_ex on rows [nscen][MSD_OV_COUNT]; fused_family: Plan::fused_family of the problem */
 Tuning &tuning();                                         /* the switches of msd_tuning() (msd_api.hip) */
 msd::KernelFn find_kernel(const msd::KernelId &id);      /* the instantiation in the kernel units (msd_kernels_*.hip); nullptr: none, also for the empty id */
 

@@ -12,6 +12,9 @@
  * kernels launched on an empty list return at once.
  * Under speed restrictions (msd_mpc_speed_restrictions) one more kernel in front of the scenario records builds the re-solve's rows of limits and the caps of the
  * end speeds from the records known by then; every launch of the re-solve, the twin's included, runs under the rows.
+ * Under rolling stock of their own (msd_mpc_rolling_stock) every launch of a re-solve takes the scenarios' override rows (the twin's with its own objective
+ * scaling, written per re-solve by mpc_twin_scaling), and with a plant mpc_plant stands where mpc_advance stood: the measured state comes from the plant
+ * integrated under the planned forces, not from the plan.
  */
 #include <hip/hip_runtime.h>
 
@@ -188,6 +191,56 @@ __global__ void mpc_advance(int B, const double *z, int nz, const double *stats,
     vnow[s] = __dmul_rn(v, __dadd_rn(1.0, __dmul_rn(noise, n2[s])));
 }
 
+/* the twin's rows of rolling stock: the model rows with MSD_OV_OBJ_DEN = the objective scaling of the twin of this re-solve (ocp.py:282: a constant of the twin's
+ * problem, not a function of the mass -- mseetc/ocp.py: minimumTime does the same per call) */
+__global__ void mpc_twin_scaling(int B, double obj_den, double *ovr_tw)
+{
+    const int s = blockIdx.x*blockDim.x + threadIdx.x;
+    if (s >= B) return;
+    ovr_tw[(size_t)MSD_OV_COUNT*s + MSD_OV_OBJ_DEN] = obj_den;
+}
+
+/*
+ * The plant advances `stride` intervals (msd_mpc_rolling_stock; mseetc/mpc.py: plantAdvance is the host statement): from the re-solve's own initial state (its
+ * scenario record) under the planned forces of its solution, interval by interval through the solver's explicit Runge-Kutta map with the plant's Davis
+ * coefficients, `steps` steps per interval, the time integrated with the same stages.  One lane per scenario.  P: the re-solve's problem record (by value; its
+ * profile pointers are read for the first `stride` intervals, stride < N).  The noise is mpc_advance's.  A scenario that stalls, has stalled or whose re-solve
+ * failed keeps its last measurement.
+ *   plant [B][MSD_MPC_PL_COUNT], stalled [B], ps [B][MSD_MPC_PS_COUNT] (the record of this advance)
+ */
+__global__ void mpc_plant(msd::DevProb P, int B, int stride, int steps, const double *z, int nz, const double *stats, const double *scen, const double *plant, double noise,
+                          const double *n1, const double *n2, double *tnow, double *vnow, int *stalled, double *ps)
+{
+    const int s = blockIdx.x*blockDim.x + threadIdx.x;
+    if (s >= B) return;
+    double *rec = ps + (size_t)MSD_MPC_PS_COUNT*s;
+    if (stalled[s] || stats[(size_t)MSD_ST_COUNT*s + MSD_ST_STATUS] < 0) {
+        rec[MSD_MPC_PS_T] = tnow[s]; rec[MSD_MPC_PS_V] = vnow[s]; rec[MSD_MPC_PS_STALLED] = stalled[s] ? 1.0 : 0.0;
+        return;
+    }
+    const double *pr = plant + (size_t)MSD_MPC_PL_COUNT*s;
+    msd::DevProb Pp = P;
+    Pp.sr0 = pr[MSD_MPC_PL_SR0]; Pp.sr1 = pr[MSD_MPC_PL_SR1]; Pp.sr2 = pr[MSD_MPC_PL_SR2];
+    Pp.numSteps = steps; Pp.numApprox = 0;
+    const double scale = pr[MSD_MPC_PL_FORCE_SCALE];
+    const int stp = 4 + P.withPn;
+    const double *zs = z + (size_t)nz*s;
+    double t = scen[(size_t)MSD_SC_COUNT*s + MSD_SC_T0], b = scen[(size_t)MSD_SC_COUNT*s + MSD_SC_V0SQ];
+    bool stall = false;
+    for (int i = 0; i < stride; i++) {
+        const double w = (zs[stp*i] + (P.withPn ? zs[stp*i + 1] : 0.0))*scale;
+        double tau, bp;
+        msd::interval_map<double>(Pp, b, w, msd::track_resistance(Pp, P.grad[i], P.curv[i]), P.ds[i], tau, bp);
+        if (!(bp >= P.vminSq) || !isfinite(tau)) { stall = true; break; }      /* (a NaN fails the comparison) */
+        t += tau; b = bp;
+    }
+    const double v = sqrt(b);
+    rec[MSD_MPC_PS_T] = t; rec[MSD_MPC_PS_V] = v; rec[MSD_MPC_PS_STALLED] = stall ? 1.0 : 0.0;
+    if (stall) { stalled[s] = 1; return; }
+    tnow[s] = fmax(__dmul_rn(t, __dadd_rn(1.0, __dmul_rn(noise, n1[s]))), 0.0);      /* (mpc_advance's arithmetic) */
+    vnow[s] = __dmul_rn(v, __dadd_rn(1.0, __dmul_rn(noise, n2[s])));
+}
+
 }  // namespace
 
 struct msd_mpc {
@@ -218,6 +271,14 @@ struct msd_mpc {
     int rs_nscen = 0, rs_max = 0;
     std::vector<double> origin;           /* [K] route coordinate of the first node of grid k */
     double last0 = 0;                     /* position of the last node of grid 0 (the checks of the records) */
+    /* rolling stock (msd_mpc_rolling_stock), one buffer: model rows | the twin's copy of them | plant rows | plant states [K-1][nscen] | stalled flags (ints);
+     * ro_nscen scenarios have records (0: none) and only a run of exactly that many is accepted */
+    double *d_ro = nullptr, *d_ovr = nullptr, *d_ovr_tw = nullptr, *d_plant = nullptr, *d_ps = nullptr;
+    int *d_stalled = nullptr;
+    int cap_ro = 0;                       /* scenarios of d_ro */
+    int ro_nscen = 0, plant_steps = 0;
+    bool ro_model = false, ro_plant = false;
+    int ps_nscen = 0;                     /* scenarios of the plant states the last run left (0: none) */
 };
 
 /* the rows and caps of re-solve k under the loop's records, on `st` */
@@ -238,7 +299,7 @@ int msd_mpc_destroy(msd_mpc_handle m)
     if (m->h) { hipSetDevice(m->h->device); hipStreamSynchronize(m->h->stream); m->h->attached_loops--; }
     if (m->twin) m->twin->attached_loops--;
     hipFree(m->d_prof); hipFree(m->d_work); hipFree(m->d_tables); hipFree(m->d_ints); hipFree(m->d_buf); hipFree(m->d_zlog);
-    hipFree(m->d_rs); hipFree(m->d_rows);
+    hipFree(m->d_rs); hipFree(m->d_rows); hipFree(m->d_ro);
     if (m->e0) hipEventDestroy(m->e0);
     if (m->e1) hipEventDestroy(m->e1);
     delete m;
@@ -377,6 +438,12 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
     if (rs && nscen != m->rs_nscen)
         return fail(MSD_E_INVALID, "the loop holds the speed restrictions of " + std::to_string(m->rs_nscen) + " scenarios, the run has " + std::to_string(nscen)
                                    + " (msd_mpc_speed_restrictions with nscen = 0 clears them)");
+    const bool ro = m->ro_nscen != 0;
+    if (ro && nscen != m->ro_nscen)
+        return fail(MSD_E_INVALID, "the loop holds the rolling stock of " + std::to_string(m->ro_nscen) + " scenarios, the run has " + std::to_string(nscen)
+                                   + " (msd_mpc_rolling_stock with nscen = 0 clears it)");
+    const double *ovr = (ro && m->ro_model) ? m->d_ovr : nullptr;      /* (every launch: the lists carry original scenario indices, so row s stays with scenario s) */
+    const bool plant = ro && m->ro_plant;
     for (int s = 0; s < nscen; s++) if (!(T[s] > 0)) return fail(MSD_E_INVALID, "Terminal time must be a strictly positive number!");
     msd_problem *h = m->h;
     if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
@@ -393,6 +460,11 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
     } else if (K > 1) {
         HIP_TRY(hipMemsetAsync(m->d_n1, 0, sizeof(double)*(size_t)(K - 1)*B, st));
         HIP_TRY(hipMemsetAsync(m->d_n2, 0, sizeof(double)*(size_t)(K - 1)*B, st));
+    }
+    if (plant) {
+        m->ps_nscen = 0;
+        HIP_TRY(hipMemsetAsync(m->d_stalled, 0, sizeof(int)*(size_t)B, st));
+        HIP_TRY(hipMemsetAsync(m->d_ps, 0, sizeof(double)*(size_t)MSD_MPC_PS_COUNT*std::max(K - 1, 1)*B, st));      /* (a record no advance writes reads as zeros) */
     }
     const dim3 tb(256), gb((B + 255)/256);
     auto queue = [&]() { int *q = m->d_queue + m->queue_slot; m->queue_slot = (m->queue_slot + 1) % RING; return q; };
@@ -422,14 +494,15 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
         ws.d_dual_out = m->warm ? m->d_dual[cur] : nullptr;
         ws.one_attempt = m->relax;      /* (mpc_relax: what the twin does not declare late is solved again with both attempts) */
         ws.use_soc = true;              /* (second-order corrections are the rule in these re-solves: the first-pass kernel that has them, msd_kernel.hpp: SOCK) */
-        rc = msd_host::launch_plan(pl, st, m->d_work, m->d_follow, queue(), B, m->d_scen, nullptr, m->d_z[cur], nullptr, m->d_st[cur], nullptr, 0, ws);
+        rc = msd_host::launch_plan(pl, st, m->d_work, m->d_follow, queue(), B, m->d_scen, ovr, m->d_z[cur], nullptr, m->d_st[cur], nullptr, 0, ws);
         if (rc != MSD_OK) { hipStreamSynchronize(st); return rc; }      /* (nothing of a loop that failed half-way stays queued on the handle's stream) */
         if (m->relax) {
             const msd_host::Plan &tw = m->tw[k];
             hipLaunchKernelGGL(mpc_collect, gb, tb, 0, st, B, m->d_st[cur], m->d_scen, 3*m->length[k]/m->vmax, m->d_flag, m->d_listA, m->d_scen_tw);
             msd_host::WarmStart wtw;
             wtw.d_limits = ws.d_limits;
-            rc = msd_host::launch_plan(tw, st, m->d_work, m->d_follow_tw, queue(), B, m->d_scen_tw, nullptr, m->d_ztw, nullptr, m->d_sttw, nullptr, 0, wtw, m->d_listA);
+            if (ovr) hipLaunchKernelGGL(mpc_twin_scaling, gb, tb, 0, st, B, tw.P.objDen, m->d_ovr_tw);
+            rc = msd_host::launch_plan(tw, st, m->d_work, m->d_follow_tw, queue(), B, m->d_scen_tw, ovr ? m->d_ovr_tw : nullptr, m->d_ztw, nullptr, m->d_sttw, nullptr, 0, wtw, m->d_listA);
             if (rc != MSD_OK) { hipStreamSynchronize(st); return rc; }
             double margin = m->margin;
             for (int a = 0; a < 3; a++, margin *= 4) {
@@ -438,7 +511,7 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
                 cold.d_dual_out = ws.d_dual_out;
                 cold.use_soc = true;
                 cold.d_limits = ws.d_limits;
-                rc = msd_host::launch_plan(pl, st, m->d_work, m->d_follow, queue(), B, m->d_scen, nullptr, m->d_z[cur], nullptr, m->d_st[cur], nullptr, 0, cold, m->d_listB);
+                rc = msd_host::launch_plan(pl, st, m->d_work, m->d_follow, queue(), B, m->d_scen, ovr, m->d_z[cur], nullptr, m->d_st[cur], nullptr, 0, cold, m->d_listB);
                 if (rc != MSD_OK) { hipStreamSynchronize(st); return rc; }
             }
         }
@@ -447,7 +520,10 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
             HIP_TRY(hipMemcpyAsync(m->d_zlog + zoff, m->d_z[cur], sizeof(double)*(size_t)pl.nz*B, hipMemcpyDeviceToDevice, st));
             zoff += (size_t)pl.nz*B;
         }
-        if (k + 1 < K && N - m->stride >= 1)
+        if (k + 1 < K && N - m->stride >= 1 && plant)
+            hipLaunchKernelGGL(mpc_plant, gb, tb, 0, st, pl.P, B, m->stride, m->plant_steps, m->d_z[cur], pl.nz, m->d_st[cur], m->d_scen, m->d_plant, m->noise,
+                               m->d_n1 + (size_t)B*k, m->d_n2 + (size_t)B*k, m->d_tnow, m->d_vnow, m->d_stalled, m->d_ps + (size_t)MSD_MPC_PS_COUNT*B*k);
+        else if (k + 1 < K && N - m->stride >= 1)
             hipLaunchKernelGGL(mpc_advance, gb, tb, 0, st, B, m->d_z[cur], pl.nz, m->d_st[cur], stp*m->stride + 2 + pl.P.withPn, stp*m->stride + 3 + pl.P.withPn, m->noise,
                                m->d_n1 + (size_t)B*k, m->d_n2 + (size_t)B*k, m->d_tnow, m->d_vnow);
         cur = prev;
@@ -458,6 +534,64 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
     if (z_log) HIP_TRY(hipMemcpyAsync(z_log, m->d_zlog, sizeof(double)*zoff, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (loop_ms) HIP_TRY(hipEventElapsedTime(loop_ms, m->e0, m->e1));
+    if (plant) m->ps_nscen = B;
+    return MSD_OK;
+}
+
+int msd_mpc_rolling_stock(msd_mpc_handle m, int nscen, const double *model, const double *plant, int plant_steps)
+{
+    if (!m) return fail(MSD_E_INVALID, "null handle");
+    if (nscen == 0) { m->ro_nscen = 0; m->ro_model = m->ro_plant = false; m->ps_nscen = 0; return MSD_OK; }      /* (the buffer stays; no run is in flight) */
+    if (nscen < 0 || (!model && !plant)) return fail(MSD_E_INVALID, "msd_mpc_rolling_stock: bad argument");
+    if (m->rs_nscen && nscen != m->rs_nscen)
+        return fail(MSD_E_INVALID, "the loop holds the speed restrictions of " + std::to_string(m->rs_nscen) + " scenarios: rolling stock of " + std::to_string(nscen) + " does not compose with them");
+    if (model) {
+        bool fused = false;      /* (any kernel of the loop that has the row structure compiled in) */
+        for (int k = 0; k < m->K; k++) fused = fused || m->pl[k].fused_family || (m->twin && m->tw[k].fused_family);
+        const int rc = msd_host::check_overrides(fused, nscen, model);
+        if (rc != MSD_OK) return rc;
+    }
+    if (plant) {
+        if (plant_steps < 1 || plant_steps > 64) return fail(MSD_E_INVALID, "msd_mpc_rolling_stock: plant_steps must be 1 ... 64");
+        for (int s = 0; s < nscen; s++) {
+            const double *r = plant + (size_t)MSD_MPC_PL_COUNT*s;
+            for (int j = 0; j < MSD_MPC_PL_COUNT; j++) if (!std::isfinite(r[j])) return fail(MSD_E_INVALID, "plant of scenario " + std::to_string(s) + " is not finite");
+            if (r[MSD_MPC_PL_SR0] < 0 || r[MSD_MPC_PL_SR1] < 0 || r[MSD_MPC_PL_SR2] < 0) return fail(MSD_E_INVALID, "plant of scenario " + std::to_string(s) + " has a negative Davis coefficient");
+            if (!(r[MSD_MPC_PL_FORCE_SCALE] > 0)) return fail(MSD_E_INVALID, "plant of scenario " + std::to_string(s) + ": force_scale must be positive");
+        }
+    }
+    msd_problem *h = m->h;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    m->ro_nscen = 0; m->ro_model = m->ro_plant = false; m->ps_nscen = 0;      /* (until the upload has ended) */
+    const size_t b = (size_t)nscen, states = (size_t)MSD_MPC_PS_COUNT*std::max(m->K - 1, 1)*b;
+    if (nscen > m->cap_ro) {
+        hipFree(m->d_ro); m->d_ro = nullptr; m->cap_ro = 0;
+        HIP_TRY(hipMalloc((void **)&m->d_ro, sizeof(double)*(2*MSD_OV_COUNT*b + MSD_MPC_PL_COUNT*b + states + b)));      /* (the flags: ints in the room of b doubles) */
+        m->cap_ro = nscen;
+    }
+    m->d_ovr = m->d_ro; m->d_ovr_tw = m->d_ovr + MSD_OV_COUNT*b; m->d_plant = m->d_ovr_tw + MSD_OV_COUNT*b; m->d_ps = m->d_plant + MSD_MPC_PL_COUNT*b;
+    m->d_stalled = (int *)(m->d_ps + states);
+    if (model) {
+        HIP_TRY(hipMemcpy(m->d_ovr, model, sizeof(double)*MSD_OV_COUNT*b, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(m->d_ovr_tw, model, sizeof(double)*MSD_OV_COUNT*b, hipMemcpyHostToDevice));      /* (mpc_twin_scaling rewrites one column per re-solve) */
+    }
+    if (plant) HIP_TRY(hipMemcpy(m->d_plant, plant, sizeof(double)*MSD_MPC_PL_COUNT*b, hipMemcpyHostToDevice));
+    m->ro_model = model != nullptr; m->ro_plant = plant != nullptr; m->plant_steps = plant ? plant_steps : 0;
+    m->ro_nscen = nscen;
+    return MSD_OK;
+}
+
+int msd_mpc_plant_states(msd_mpc_handle m, double *states)
+{
+    if (!m || !states) return fail(MSD_E_INVALID, "bad argument");
+    if (!m->ro_nscen || !m->ro_plant) return fail(MSD_E_INVALID, "the loop holds no plant (msd_mpc_rolling_stock)");
+    if (!m->ps_nscen) return fail(MSD_E_INVALID, "msd_mpc_plant_states: the loop has not run under its plant yet");
+    if (m->K < 2) return MSD_OK;
+    msd_problem *h = m->h;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(states, m->d_ps, sizeof(double)*(size_t)MSD_MPC_PS_COUNT*(m->K - 1)*m->ps_nscen, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MSD_OK;
 }
 
@@ -466,6 +600,8 @@ int msd_mpc_speed_restrictions(msd_mpc_handle m, const double *origin, int nscen
     if (!m) return fail(MSD_E_INVALID, "null handle");
     if (nscen == 0) { m->rs_nscen = 0; return MSD_OK; }      /* (the buffers stay; no run is in flight: msd_mpc_run waits for its own end) */
     if (nscen < 0 || !origin || !count || !records) return fail(MSD_E_INVALID, "msd_mpc_speed_restrictions: bad argument");
+    if (m->ro_nscen && nscen != m->ro_nscen)
+        return fail(MSD_E_INVALID, "the loop holds the rolling stock of " + std::to_string(m->ro_nscen) + " scenarios: speed restrictions of " + std::to_string(nscen) + " do not compose with it");
     if (max_per_scenario < 1 || max_per_scenario > MSD_RS_MAX)
         return fail(MSD_E_INVALID, "msd_mpc_speed_restrictions: max_per_scenario must be 1 ... " + std::to_string(MSD_RS_MAX));
     const int K = m->K;

@@ -64,6 +64,9 @@ class MpcPlan(ctypes.Structure):
 
 MPC = dict(T0=0, V0=1, T=2, STATUS=3, ITERS=4, OBJ=5, RELAXED=6, COUNT=7)      # MSD_MPC_*
 MPC_RS_COUNT = 4      # MSD_MPC_RS_COUNT: (begin [m], end [m], velocity [m/s], first_resolve) of a speed restriction inside the loop
+MPC_PL = dict(SR0=0, SR1=1, SR2=2, FORCE_SCALE=3, COUNT=4)      # MSD_MPC_PL_*: the plant of a scenario (msd_mpc_rolling_stock)
+MPC_PS = dict(T=0, V=1, STALLED=2, COUNT=3)                      # MSD_MPC_PS_*: the plant's state behind an advance (msd_mpc_plant_states)
+MPC_PLANT_STEPS_MAX = 64
 
 
 class DeviceError(RuntimeError):
@@ -144,6 +147,8 @@ def lib():
         L.msd_mpc_nz.argtypes = [vp, ctypes.c_int]
         L.msd_mpc_speed_restrictions.argtypes = [vp, _dptr, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _dptr]
         L.msd_mpc_limit_rows.argtypes = [vp, ctypes.c_int, _dptr]
+        L.msd_mpc_rolling_stock.argtypes = [vp, ctypes.c_int, _dptr, _dptr, ctypes.c_int]
+        L.msd_mpc_plant_states.argtypes = [vp, _dptr]
 
         _lib = L
 
@@ -778,6 +783,41 @@ class DeviceLoop():
         rows = np.zeros((int(B), self._descs[int(k)].num_intervals + 1))
         _check(lib().msd_mpc_limit_rows(self._m, int(k), _d(rows)))
         return rows
+
+    def rolling_stock(self, model=None, plant=None, plantSteps=8):
+        """
+        Rolling stock inside the loop (msd_mpc_rolling_stock): model (B, OV['COUNT']) override rows of the scenarios' own trains (casadiSolver._overrides) or
+        None, plant (B, MPC_PL['COUNT']) rows of the plants or None, plantSteps Runge-Kutta steps per interval of the plant.  Every run of exactly B scenarios
+        is under them until they are cleared.  Both None: clears them.
+        """
+
+        L = lib()
+        if model is None and plant is None:
+            _check(L.msd_mpc_rolling_stock(self._m, 0, None, None, 0))
+            self._ro = 0
+            return self
+        rows = []
+        for a, width, what in ((model, OV['COUNT'], 'model'), (plant, MPC_PL['COUNT'], 'plant')):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.ndim != 2 or a.shape[1] != width:
+                    raise ValueError("{} rows must have shape (B, {})!".format(what, width))
+            rows.append(a)
+        model, plant = rows
+        if model is not None and plant is not None and model.shape[0] != plant.shape[0]:
+            raise ValueError("model rows of {} scenarios, plant rows of {}!".format(model.shape[0], plant.shape[0]))
+        B = (model if model is not None else plant).shape[0]
+        _check(L.msd_mpc_rolling_stock(self._m, B, _d(model) if model is not None else None, _d(plant) if plant is not None else None, int(plantSteps)))
+        self._ro = B if plant is not None else 0
+        return self
+
+    def plant_states(self):
+        "(K - 1, B, MPC_PS['COUNT']): the plant's state behind every advance of the last run, before the noise (msd_mpc_plant_states)."
+
+        B = getattr(self, '_ro', 0)
+        states = np.zeros((max(self.K - 1, 0), max(B, 1), MPC_PS['COUNT']))
+        _check(lib().msd_mpc_plant_states(self._m, _d(states)))
+        return states[:, :B]
 
     def close(self):
 

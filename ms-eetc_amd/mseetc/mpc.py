@@ -141,6 +141,103 @@ def _restrictionsOfResolve(sets, k, origin, positions):
     return out
 
 
+def _rollingStock(train, B, mass, r0, r1, r2, plantMass, plantR0, plantR1, plantR2, plantSteps):
+    """
+    Rolling stock of a loop (include/mseetc_mpc.h: msd_mpc_rolling_stock), validated: the model's `mass`, `r0`, `r1`, `r2` as casadiSolver.solveBatch takes them
+    (SI units, scalars or one value per scenario; None: the train's) and the plant's -- the train that actually runs; a plant value that is not given is the
+    scenario's model value.  Returns (model, plant): `model` a dict of (B,) arrays mass, r0, r1, r2, or None when none of them is given; `plant` the
+    (B, MPC_PL['COUNT']) rows (specific Davis coefficients of the plant, force_scale = M_model/M_plant), or None when no plant value is given.
+    """
+
+    from ._device import MPC_PL, MPC_PLANT_STEPS_MAX
+
+    def full(a, default, what):
+        a = np.asarray(default if a is None else a, dtype=float)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
+            raise ValueError("{} of {} scenarios for a batch of {}!".format(what, a.shape[0] if a.ndim == 1 else a.shape, B))
+        return np.broadcast_to(a, (B,)).copy()
+
+    given = [a is not None for a in (mass, r0, r1, r2)]
+    m = dict(mass=full(mass, train.mass, 'mass'), r0=full(r0, train.r0, 'r0'), r1=full(r1, train.r1, 'r1'), r2=full(r2, train.r2, 'r2'))
+    if not all(np.all(np.isfinite(a)) for a in m.values()) or np.any(m['mass'] <= 0) or any(np.any(m[k] < 0) for k in ('r0', 'r1', 'r2')):
+        raise ValueError("Train mass must be positive and rolling resistance coefficients non-negative!")
+
+    plant = None
+    if any(a is not None for a in (plantMass, plantR0, plantR1, plantR2)):
+        if int(plantSteps) != plantSteps or not 1 <= int(plantSteps) <= MPC_PLANT_STEPS_MAX:
+            raise ValueError("plantSteps must be 1 ... {}!".format(MPC_PLANT_STEPS_MAX))
+        pm, p0, p1, p2 = (full(plantMass, m['mass'], 'plantMass'), full(plantR0, m['r0'], 'plantR0'), full(plantR1, m['r1'], 'plantR1'),
+                          full(plantR2, m['r2'], 'plantR2'))
+        if not all(np.all(np.isfinite(a)) for a in (pm, p0, p1, p2)) or np.any(pm <= 0) or np.any(p0 < 0) or np.any(p1 < 0) or np.any(p2 < 0):
+            raise ValueError("Plant mass must be positive and its rolling resistance coefficients non-negative!")
+        M = pm*train.rho
+        plant = np.zeros((B, MPC_PL['COUNT']))
+        plant[:, MPC_PL['SR0']], plant[:, MPC_PL['SR1']], plant[:, MPC_PL['SR2']] = p0/M, p1/M, p2/M
+        plant[:, MPC_PL['FORCE_SCALE']] = (m['mass']*train.rho)/M
+
+    return (m if any(given) else None), plant
+
+
+def _plantAdvance(points, withPnBrake, g, rho, vminSq, z, t0, v0sq, plantRows, plantSteps, stride):
+    "plantAdvance behind the solver: `points` the grid frame (computeDiscretizationPoints), g and rho the train's, vminSq the square of the minimum velocity."
+
+    from ._device import MPC_PL
+
+    z = np.atleast_2d(np.asarray(z, dtype=float))
+    rows = np.atleast_2d(np.asarray(plantRows, dtype=float))
+    B = z.shape[0]
+    pn = int(bool(withPnBrake))
+    stp = 4 + pn
+    pos = points.index.values.astype(float)
+    ds = np.diff(pos)
+    grad = points['Gradient [permil]'].values.astype(float)/1e3
+    curv = np.abs(points['Curvature [1/m]'].values.astype(float))
+    sr0, sr1, sr2, scale = rows[:, MPC_PL['SR0']], rows[:, MPC_PL['SR1']], rows[:, MPC_PL['SR2']], rows[:, MPC_PL['FORCE_SCALE']]
+    t = np.broadcast_to(np.asarray(t0, dtype=float), (B,)).copy()
+    b = np.broadcast_to(np.asarray(v0sq, dtype=float), (B,)).copy()
+    stalled = np.zeros(B, dtype=bool)
+    n = int(plantSteps)
+    h = 1.0/n
+
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        for i in range(int(stride)):
+            c = curv[i]
+            cr = g*0.5*c/(1 - 30*c) if c <= 1.0/300.0 else g*0.65*c/(1 - 55*c)      # train.py:252-253
+            G = g*grad[i]*(1/rho) + cr*(1/rho)
+            w = (z[:, stp*i] + (z[:, stp*i + 1] if pn else 0.0))*scale
+            fb = lambda x: ((w - (sr0 + (np.sqrt(x)*sr1 + x*sr2))) - G)*(2*ds[i])      # d(b)/d(sigma) on the unit interval (train.py:251-259)
+            ft = lambda x: ds[i]/np.sqrt(x)                                             # d(t)/d(sigma)
+            bi, tau = b.copy(), np.zeros(B)
+            for _ in range(n):
+                k1b, k1t = fb(bi), ft(bi)
+                b2 = bi + k1b*(0.5*h)
+                k2b, k2t = fb(b2), ft(b2)
+                b3 = bi + k2b*(0.5*h)
+                k3b, k3t = fb(b3), ft(b3)
+                b4 = bi + k3b*h
+                k4b, k4t = fb(b4), ft(b4)
+                bi = bi + ((k1b + k2b*2.0) + (k3b*2.0 + k4b))*(h/6)
+                tau = tau + ((k1t + k2t*2.0) + (k3t*2.0 + k4t))*(h/6)
+            stalled |= ~stalled & (~(bi >= vminSq) | ~np.isfinite(tau))      # (a NaN fails the comparison)
+            t = np.where(stalled, t, t + tau)
+            b = np.where(stalled, b, bi)
+
+    return t, np.sqrt(b), stalled
+
+
+def plantAdvance(solver, z, t0, v0sq, plantRows, plantSteps, stride):
+    """
+    The plant of a loop advances `stride` intervals of the solver's grid: the numpy statement of csrc/msd_mpc.hip: mpc_plant, the definition the device is held to.
+    From the re-solve's own initial state (`t0` (B,), `v0sq` (B,): t0 and the clipped v0^2 of its scenario records) under the planned forces of its solutions
+    `z` (B, nz): interval i < stride runs under w_i = (Fel_i + Fpb_i) force_scale through explicit Runge-Kutta of 4th order in the space domain, `plantSteps` steps,
+    time and b = v^2 integrated jointly (the interval map of the solver with numSteps = plantSteps, numApproxSteps = 0), with the plant's specific Davis
+    coefficients of `plantRows` (B, MPC_PL['COUNT']) and the train's g and rho.  After an interval, b+ < vmin^2 (or a NaN, or a running time that is not finite) marks
+    the scenario stalled: it stays at the state in front of that interval.  Returns (t (B,), v (B,), stalled (B,) bool), before any noise.
+    """
+
+    return _plantAdvance(solver.points, solver.withPnBrake, solver.train.g, solver.train.rho, float(solver.velocityMin)**2, z, t0, v0sq, plantRows, plantSteps, stride)
+
+
 class DeviceLoop():
     """
     The shrinking-horizon loop with its bookkeeping on the device (csrc/msd_mpc.hip, include/mseetc_mpc.h): the grid sequence does not depend
@@ -253,7 +350,8 @@ class DeviceLoop():
         scen = solver._scenarios(terminalTime, initialTime, self.terminalVelocity, initialVelocity, rs)
         return np.broadcast_to(scen, (int(B), scen.shape[1])).copy()
 
-    def run(self, terminalTime, seed=0, initialTime=0.0, initialVelocity=1.0, keepZ=True, speedRestrictions=None):
+    def run(self, terminalTime, seed=0, initialTime=0.0, initialVelocity=1.0, keepZ=True, speedRestrictions=None, mass=None, r0=None, r1=None, r2=None,
+            plantMass=None, plantR0=None, plantR1=None, plantR2=None, plantSteps=8):
         """
         One loop; returns the log of shrinkingHorizon() (list of dicts per re-solve; 'z' None without keepZ) -- `loop_ms` in every entry is the device time of the whole loop.
         `speedRestrictions`: a sequence of B sequences of (begin [m], end [m], velocity [m/s][, firstResolve]), or one such sequence for every scenario --
@@ -261,9 +359,15 @@ class DeviceLoop():
         scenario's re-solves run under restrictedLimits(k, ...), their end speeds clipped to the restricted limits; a restriction the train has passed is
         ignored.  ValueError: a record that is not finite, ends at or before its beginning, restricts no interval of the first grid, is not above the minimum
         velocity or names no re-solve of the loop; more than 16 per scenario; a wrong batch length.  The records are the loop's for this run only.
+        `mass`, `r0`, `r1`, `r2` (SI units, scalars or one value per scenario): the scenarios' own rolling stock, as in casadiSolver.solveBatch -- what the controller
+        believes its train to be, in every re-solve, the minimum running times included.  `plantMass`, `plantR0`, `plantR1`, `plantR2`: the train that actually runs
+        (a value that is not given is the scenario's model value).  With any of them the state a re-solve starts from is no longer read from the previous plan: the
+        plant is integrated under the planned forces (plantAdvance, `plantSteps` Runge-Kutta steps per interval), and the log entries in front of the last one gain
+        'tPlant', 'vPlant' (the plant's state behind the advance, before the noise) and 'stalled' (the plant fell below the minimum velocity in this or an earlier
+        advance: the scenario keeps its last measurement).  ValueError: values the library refuses, plantSteps outside 1 ... 64, a wrong batch length.
         """
 
-        from ._device import MPC, MPC_RS_COUNT
+        from ._device import MPC, MPC_PS
 
         T = np.array(np.atleast_1d(np.asarray(terminalTime, dtype=float)), copy=True)
         B = T.shape[0]
@@ -272,13 +376,23 @@ class DeviceLoop():
         n1, n2 = np.zeros((max(self.K - 1, 0), B)), np.zeros((max(self.K - 1, 0), B))
         for k in range(self.K - 1):      # (the order of shrinkingHorizon's draws)
             n1[k], n2[k] = rng.standard_normal(B), rng.standard_normal(B)
-        if sets is not None and any(sets):
+        model, plant = _rollingStock(self.solvers[0].train, B, mass, r0, r1, r2, plantMass, plantR0, plantR1, plantR2, plantSteps)
+        rows = self.solvers[0]._overrides(B, model['mass'], model['r0'], model['r1'], model['r2']) if model is not None else None      # (the rule of solveBatch)
+        restricted = sets is not None and any(sets)
+        states = None
+        if restricted or rows is not None or plant is not None:
             try:
-                self.device.speed_restrictions(*self.restrictionRecords(sets, B))
+                if restricted:
+                    self.device.speed_restrictions(*self.restrictionRecords(sets, B))
+                if rows is not None or plant is not None:
+                    self.device.rolling_stock(rows, plant, plantSteps)
                 log, zs, ms = self.device.run(T, initialTime, initialVelocity, n1, n2, keepZ=keepZ)
+                if plant is not None and self.K > 1:
+                    states = self.device.plant_states()
             finally:
+                self.device.rolling_stock(None)
                 self.device.speed_restrictions(None)
-        else:      # (no scenario is restricted: the plain loop)
+        else:      # (no scenario is restricted or has a train of its own: the plain loop)
             log, zs, ms = self.device.run(T, initialTime, initialVelocity, n1, n2, keepZ=keepZ)
         out = []
         for k in range(self.K):
@@ -287,6 +401,8 @@ class DeviceLoop():
                             T=r[:, MPC['T']].copy(), status=r[:, MPC['STATUS']].astype(int), iterations=r[:, MPC['ITERS']].astype(int),
                             cost=r[:, MPC['OBJ']]*self.scale, z=zs[k] if zs is not None else None, relaxed=r[:, MPC['RELAXED']] > 0,
                             kernel_ms=ms/self.K, loop_ms=ms))
+            if states is not None and k < self.K - 1:
+                out[-1].update(tPlant=states[k, :, MPC_PS['T']].copy(), vPlant=states[k, :, MPC_PS['V']].copy(), stalled=states[k, :, MPC_PS['STALLED']] > 0)
         return out
 
     def close(self):
@@ -302,7 +418,7 @@ class DeviceLoop():
 def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2, noise=0.0, seed=0,
                      initialTime=0.0, initialVelocity=1.0, terminalVelocity=1.0, device=0, solverFactory=None,
                      warmStart=False, warmMu=1e-2, warmPush=1e-3, dualMu=1e-4, relaxInfeasible=True, lateMargin=5e-3, onDevice=False,
-                     speedRestrictions=None):
+                     speedRestrictions=None, mass=None, r0=None, r1=None, r2=None, plantMass=None, plantR0=None, plantR1=None, plantR2=None, plantSteps=8):
     """
     Re-solve `numResolves` times; after each solve the train advances `stride` intervals of the current grid, the
     measured time and speed at that node are perturbed by `noise` (relative, standard normal) and the remaining
@@ -326,6 +442,11 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
     DeviceLoop.run.  From re-solve `firstResolve` on the scenario is solved under the restriction (casadiSolver.solveBatch(speedRestrictions=...) on the grid
     of the re-solve), its minimum running time is the one under the restriction, and a restriction the train has passed is ignored.  A substituted solver
     must accept the keyword `speedRestrictions` in solveBatch.
+
+    `mass`, `r0`, `r1`, `r2`: the scenarios' own rolling stock (casadiSolver.solveBatch) in every re-solve and in the minimum running times; `plantMass`,
+    `plantR0`, `plantR1`, `plantR2`, `plantSteps`: the train that actually runs, as in DeviceLoop.run -- with any of them the measured state comes from plantAdvance
+    under the planned forces instead of the plan, and the log entries in front of the last one gain 'tPlant', 'vPlant' and 'stalled'.  A substituted solver must
+    accept the keywords `mass`, `r0`, `r1`, `r2` in solveBatch when any of them is given, and with a plant return its (B, 4) scenario records as 'scenarios'.
     """
 
     if onDevice:
@@ -335,7 +456,8 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
         loop = DeviceLoop(train, track, optsDict, numResolves, stride=stride, noise=noise, terminalVelocity=terminalVelocity, device=device, warmStart=warmStart,
                           warmPush=warmPush, dualMu=dualMu, relaxInfeasible=relaxInfeasible, lateMargin=lateMargin)
         try:
-            return loop.run(terminalTime, seed=seed, initialTime=initialTime, initialVelocity=initialVelocity, speedRestrictions=speedRestrictions)
+            return loop.run(terminalTime, seed=seed, initialTime=initialTime, initialVelocity=initialVelocity, speedRestrictions=speedRestrictions,
+                            mass=mass, r0=r0, r1=r1, r2=r2, plantMass=plantMass, plantR0=plantR0, plantR1=plantR1, plantR2=plantR2, plantSteps=plantSteps)
         finally:
             loop.close()
 
@@ -345,6 +467,12 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
     T = np.array(np.atleast_1d(np.asarray(terminalTime, dtype=float)), copy=True)
     B = T.shape[0]
     rng = np.random.default_rng(seed)
+    model, plant = _rollingStock(train, B, mass, r0, r1, r2, plantMass, plantR0, plantR1, plantR2, plantSteps)
+    own = (lambda idx=slice(None): {key: a[idx] for key, a in model.items()}) if model is not None else (lambda idx=None: {})
+    stalled = np.zeros(B, dtype=bool)
+    if plant is not None:
+        from .ocp import OptionsCasadiSolver
+        vminPlant = float(OptionsCasadiSolver(optsDict).minimumVelocity)
 
     N = int(optsDict.get('numIntervals', 100))
     t_now = np.full(B, float(initialTime))
@@ -400,7 +528,7 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
                     solver.problem.keep_duals(True)      # the multipliers of every solve stay on the device for the next re-solve
                     solver.problem.direct_results(False)      # ... and so do the solutions: the shifted warm start reads them there
 
-            common = dict(initialTime=t_now, terminalVelocity=terminalVelocity, initialVelocity=v_now)
+            common = dict(initialTime=t_now, terminalVelocity=terminalVelocity, initialVelocity=v_now, **own())
 
             setsNow = None
             if speedRestrictions is not None:
@@ -444,13 +572,14 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
             if relaxInfeasible and bad.size and hasattr(solver, 'minimumTime'):
                 # what stops these scenarios is their arrival time: the minimum running time from the measured state (time-optimal twin of
                 # this re-solve's problem) tells, and becomes the new arrival time where it is later than the one asked for
+                ovBad = dict(overrides=solver._overrides(bad.size, **own(bad))) if model is not None else {}      # (minimumTime gives the rows the twin's own objective scaling)
                 if setsNow is None:
                     scenBad = solver._scenarios(T[bad], t_now[bad], terminalVelocity, v_now[bad])
-                    tmin, okMin = solver.minimumTime(scenBad)
+                    tmin, okMin = solver.minimumTime(scenBad, **ovBad)
                 else:
                     setsBad = [setsNow[i] for i in bad]
                     scenBad = solver._scenarios(T[bad], t_now[bad], terminalVelocity, v_now[bad], solver._restrictions(setsBad))
-                    tmin, okMin = solver.minimumTime(scenBad, speedRestrictions=setsBad)
+                    tmin, okMin = solver.minimumTime(scenBad, speedRestrictions=setsBad, **ovBad)
                 late = okMin & (tmin > (T[bad] - t_now[bad]))
                 if late.any():
                     idx, tm = bad[late], tmin[late]
@@ -460,7 +589,8 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
                         # (an interior-point solve needs some room above the minimum running time: a scenario that still breaks down gets four times the margin)
                         T[idx] = t_now[idx] + tm*(1 + margin)
                         under = {} if setsNow is None else dict(speedRestrictions=[setsNow[i] for i in idx])
-                        again = solver.solveBatch(T[idx], initialTime=t_now[idx], terminalVelocity=terminalVelocity, initialVelocity=v_now[idx], classifyFailures=False, **under)
+                        again = solver.solveBatch(T[idx], initialTime=t_now[idx], terminalVelocity=terminalVelocity, initialVelocity=v_now[idx], classifyFailures=False, **under,
+                                                  **own(idx))
                         for key in ('z', 'status', 'iterations', 'cost'):
                             res[key][idx] = again[key]
                         kernel_extra += float(again.get('kernel_ms', 0.0))
@@ -491,6 +621,20 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
             # failed scenarios keep coasting on their last measurement
             ok = res['status'] >= 0
             n1, n2 = rng.standard_normal(B), rng.standard_normal(B)
+            if plant is not None and k + 1 < numResolves:      # (behind the last re-solve nothing is measured any more)
+                # the train that runs is the plant, not the plan: from the re-solve's own initial state under the planned forces (include/mseetc_mpc.h: msd_mpc_rolling_stock)
+                # (its clipped v0^2: the scenario records of the solve, under the restrictions of this re-solve)
+                if 'scenarios' in res:
+                    scenNow = np.asarray(res['scenarios'])
+                elif hasattr(solver, '_scenarios'):
+                    scenNow = solver._scenarios(T, t_now, terminalVelocity, v_now, solver._restrictions(setsNow) if setsNow is not None else None)
+                else:
+                    raise ValueError("With a plant a substituted solver returns its scenario records as 'scenarios' from solveBatch!")
+                tP, vP, now = _plantAdvance(solver.points, solver.withPnBrake, train.g, train.rho, vminPlant**2, res['z'], t_now, scenNow[:, 2], plant, plantSteps, stride)
+                moved = ok & ~stalled      # (a scenario whose re-solve failed or that has stalled keeps its last measurement: its record holds that)
+                stalled = stalled | (moved & now)
+                log[-1].update(tPlant=np.where(moved, tP, t_now), vPlant=np.where(moved, vP, v_now), stalled=stalled.copy())
+                t_meas, v_meas, ok = tP, vP, moved & ~now
             t_now = np.where(ok, np.maximum(t_meas*(1 + noise*n1), 0.0), t_now)
             v_now = np.where(ok, v_meas*(1 + noise*n2), v_now)
 
