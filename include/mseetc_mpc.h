@@ -128,7 +128,7 @@ int msd_mpc_limit_rows(msd_mpc_handle m, int k, double *rows);
  *
  * MSD_E_INVALID: nscen < 0; both arrays NULL with nscen > 0; a model row msd_solve_batch_ex refuses; a plant row that is not finite, has a negative Davis
  * coefficient or force_scale <= 0; plant_steps outside 1 ... 64 (with a plant); a count other than that of the speed restrictions the loop holds.
- * Not built: a plant rho, adhesion or force limits of its own; a plant for the loss model; disturbance estimation.
+ * Not built: a plant rho, adhesion or force limits of its own; disturbance estimation.  (The energy the closed loop really spends: msd_mpc_energy.)
  */
 enum { MSD_MPC_PL_SR0 = 0, MSD_MPC_PL_SR1, MSD_MPC_PL_SR2,   /* specific Davis coefficients of the plant (per kg of ITS mass*rho) */
        MSD_MPC_PL_FORCE_SCALE,                               /* (mass*rho of the scenario's model) / (mass*rho of the plant): commanded newtons -> plant's specific force */
@@ -143,6 +143,45 @@ int msd_mpc_rolling_stock(msd_mpc_handle m, int nscen, const double *model, cons
  */
 enum { MSD_MPC_PS_T = 0, MSD_MPC_PS_V, MSD_MPC_PS_STALLED, MSD_MPC_PS_COUNT };
 int msd_mpc_plant_states(msd_mpc_handle m, double *states);
+
+/*
+ * The energy account of the closed loop: what the train really spent, leg by leg, kept on the device while the loop runs (the reference's accounting,
+ * utils.py:243-257 and :291, Energy [kWh] = (1e-6/3.6) ds F + losses; mseetc/mpc.py: plantEnergy is the host statement the kernel is held to).
+ *
+ * A leg is what is driven behind a re-solve: the first `stride` intervals of its plan behind re-solve k < K-1 (record k), and behind the last re-solve the whole
+ * remaining plan, N_{K-1} intervals (record K-1, the final leg: no noise, nothing is measured any more).  Forces in newtons are the plan's specific forces times
+ * the total mass of the scenario's MODEL: total_mass = mass rho of the problems' train, or MSD_OV_TOTAL_MASS of the scenario's model row where the loop holds one
+ * and it is non-zero -- the plant's traction equipment receives the commanded newtons whatever the plant weighs.
+ * Speed trajectory.  With a plant (msd_mpc_rolling_stock) it is the plant's: one kernel per advance does state and account together, and time, speed, plant
+ * states and stall flags come out bit for bit as without the account; a stall ends the leg in front of the interval that stalled it, and what was spent up to
+ * there counts.  Without a plant the plan is the plant: an account kernel runs next to the advance, every interval restarts from the plan's own b_i and is
+ * integrated with the model's Davis coefficients (what the reference's post-processing does per interval), and the state at the end is the plan's node, read.
+ * Per interval, summed over the intervals completed:  traction = ds max(F_el, 0), regenerated = ds min(F_el, 0), pnBrake = ds F_pn, and losses --
+ *   eta given ([nscen][2]: etaTraction, etaRgBrake of the PLANT, which need not be the model's) or loss_kind 1: ds (ct max(F, 0) + cr max(-F, 0)), ct = (1 - eta_t)/eta_t,
+ *     cr = 1 - eta_r (closed form: the speed cancels, train.py:199-212);
+ *   loss_kind 2 without eta: the integral of L(F_el, v)/v over the interval as a third component of the Runge-Kutta steps of the trajectory (`steps` per interval),
+ *     k_E(x) = ds L(F, sqrt(x))/sqrt(x) at the four stage values of b, L the loop's own copy of the loss table with the scenario's total mass;
+ *   loss_kind 0 without eta: 0.
+ * A scenario that is not advanced (its re-solve failed, or it stalled in an earlier leg) has a zero record with 0 intervals.
+ *
+ * The account is state of the loop exactly like restrictions and rolling stock: every msd_mpc_run with exactly nscen scenarios keeps it; nscen = 0 clears it
+ * (the other arguments are ignored); a run with another count returns MSD_E_INVALID and enqueues nothing; a refused call leaves the previous state in place; the
+ * count must agree with those of the restrictions and the rolling stock the loop holds (the later call is refused otherwise).  steps: the plant's plant_steps where
+ * the loop holds a plant (it must equal it, at the call and at the run), 1 ... 64 otherwise.  Without the account the loop launches exactly what it launched
+ * before this entry point existed.  Nothing is waited for and nothing crosses PCIe inside the loop.
+ *
+ * MSD_E_INVALID: a null handle; nscen < 0; total_mass not finite or <= 0; an efficiency outside (0, 1]; steps out of range or other than the plant's; a count other
+ * than that of the restrictions or rolling stock the loop holds; records asked for before a run under the account.
+ */
+enum { MSD_MPC_EN_TRACTION = 0, MSD_MPC_EN_REGENERATED, MSD_MPC_EN_PNBRAKE, MSD_MPC_EN_LOSSES,   /* kWh */
+       MSD_MPC_EN_T, MSD_MPC_EN_V,          /* state at the end of the leg, before the noise */
+       MSD_MPC_EN_INTERVALS,                /* intervals completed in this leg */
+       MSD_MPC_EN_COUNT };
+int msd_mpc_energy(msd_mpc_handle m, int nscen, double total_mass, const double *eta /* [nscen][2] or NULL */, int steps);
+
+/* The account of every leg of the last run: records[K][nscen][MSD_MPC_EN_COUNT] (host); record K-1 is the final leg, whose MSD_MPC_EN_T / _V are the arrival:
+ * the plant's with a plant, the plan's t_N and sqrt(b_N) without one.  MSD_E_INVALID: the loop keeps no account, or has not run under it yet. */
+int msd_mpc_energy_records(msd_mpc_handle m, double *records /* [K][nscen][MSD_MPC_EN_COUNT], host */);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@
  * Under rolling stock of their own (msd_mpc_rolling_stock) every launch of a re-solve takes the scenarios' override rows (the twin's with its own objective
  * scaling, written per re-solve by mpc_twin_scaling), and with a plant mpc_plant stands where mpc_advance stood: the measured state comes from the plant
  * integrated under the planned forces, not from the plan.
+ * Under the energy account (msd_mpc_energy) mpc_energy keeps the kWh of every leg: with a plant it stands where mpc_plant stood (state and account in one
+ * launch), without one it runs next to mpc_advance; behind the last re-solve's log it runs once more over the whole last plan.
  */
 #include <hip/hip_runtime.h>
 
@@ -241,6 +243,101 @@ __global__ void mpc_plant(msd::DevProb P, int B, int stride, int steps, const do
     vnow[s] = __dmul_rn(v, __dadd_rn(1.0, __dmul_rn(noise, n2[s])));
 }
 
+/* the loss integral of one interval [Nm]: d(E)/d(sigma) = ds L(F, sqrt(b))/sqrt(b) as a third component of the Runge-Kutta steps of interval_map's joint branch
+ * (numSteps steps, the same stage values of b), L [W] = the specific losses of the table times the scenario's total mass.  With a plant the b trajectory of an
+ * interval is therefore integrated twice: here for the stages of E, and by interval_map for the state, whose bits must be mpc_plant's.  The stage arithmetic below
+ * restates that branch of interval_map (msd_kernel.hpp: numApprox == 0); should it change there, it changes here -- the statement (mseetc/mpc.py: _plantEnergy)
+ * integrates b, t and E jointly, and tests/test_mpc_energy_gpu.py holds the table losses to it at rounding level */
+__device__ __forceinline__ double loss_integral(const msd::DevProb &Pp, const msd::DynLoss &D, double b, double w, double f, double G, double ds)
+{
+    const bool traction = f >= 0;
+    const auto ke = [&](double x) { const double v = sqrt(x); return ds*(msd::spec_losses(D, traction, f, v).v*D.M)/v; };
+    const double h = 1.0/Pp.numSteps;
+    double E = 0;
+    for (int s = 0; s < Pp.numSteps; s++) {
+        const double k1b = msd::ode_b(Pp, b, w, G, ds), k1e = ke(b);
+        const double b2 = b + k1b*(0.5*h);
+        const double k2b = msd::ode_b(Pp, b2, w, G, ds), k2e = ke(b2);
+        const double b3 = b + k2b*(0.5*h);
+        const double k3b = msd::ode_b(Pp, b3, w, G, ds), k3e = ke(b3);
+        const double b4 = b + k3b*h;
+        const double k4b = msd::ode_b(Pp, b4, w, G, ds), k4e = ke(b4);
+        b = b + ((k1b + k2b*2.0) + (k3b*2.0 + k4b))*(h/6);
+        E = E + ((k1e + k2e*2.0) + (k3e*2.0 + k4e))*(h/6);
+    }
+    return E;
+}
+
+/*
+ * The energy account of one leg (msd_mpc_energy; mseetc/mpc.py: plantEnergy is the host statement): the first n intervals of the re-solve's solutions, one lane per
+ * scenario.  plant != null: the trajectory is the plant's, integrated exactly as mpc_plant integrates it -- and with `advance` this kernel stands where mpc_plant
+ * stood: it writes the record of the advance, the stall flag and the measured state as well (bit for bit mpc_plant's).  plant == null: the plan is the plant, every
+ * interval restarts from the plan's own b_i under the model's Davis coefficients (the scenario's row of `ovr`, or the problem's), the state at the end is the
+ * plan's node n.  advance == 0 (the final leg, n = N; any leg without a plant): nothing but the account is written.
+ *   coef [B][2] (ct, cr of the plants' own efficiencies) or null: the problem's loss model; en [B][MSD_MPC_EN_COUNT] (the record of this leg)
+ */
+__global__ void mpc_energy(msd::DevProb P, int B, int n, int steps, const double *z, int nz, const double *stats, const double *scen, const double *ovr, const double *plant,
+                           const double *coef, double total_mass, int advance, double noise, const double *n1, const double *n2, double *tnow, double *vnow, int *stalled,
+                           double *ps, double *en)
+{
+    const int s = blockIdx.x*blockDim.x + threadIdx.x;
+    if (s >= B) return;
+    double *e = en + (size_t)MSD_MPC_EN_COUNT*s;
+    double *rec = advance ? ps + (size_t)MSD_MPC_PS_COUNT*s : nullptr;
+    const bool was = plant && stalled[s];
+    if (was || stats[(size_t)MSD_ST_COUNT*s + MSD_ST_STATUS] < 0) {
+        if (advance) { rec[MSD_MPC_PS_T] = tnow[s]; rec[MSD_MPC_PS_V] = vnow[s]; rec[MSD_MPC_PS_STALLED] = was ? 1.0 : 0.0; }
+        for (int j = 0; j < MSD_MPC_EN_COUNT; j++) e[j] = 0.0;      /* (not advanced: a zero record with 0 intervals) */
+        return;
+    }
+    const double *row = ovr ? ovr + (size_t)MSD_OV_COUNT*s : nullptr;
+    const double M = (row && row[MSD_OV_TOTAL_MASS] != 0) ? row[MSD_OV_TOTAL_MASS] : total_mass;
+    msd::DevProb Pp = P;
+    double scale = 1.0;
+    if (plant) {
+        const double *pr = plant + (size_t)MSD_MPC_PL_COUNT*s;
+        Pp.sr0 = pr[MSD_MPC_PL_SR0]; Pp.sr1 = pr[MSD_MPC_PL_SR1]; Pp.sr2 = pr[MSD_MPC_PL_SR2];
+        scale = pr[MSD_MPC_PL_FORCE_SCALE];
+    } else if (row) { Pp.sr0 = row[MSD_OV_SR0]; Pp.sr1 = row[MSD_OV_SR1]; Pp.sr2 = row[MSD_OV_SR2]; }
+    Pp.numSteps = steps; Pp.numApprox = 0;
+    const int kind = coef ? 1 : P.lossKind;
+    const double ct = coef ? coef[2*s] : P.ct, cr = coef ? coef[2*s + 1] : P.cr;
+    const int stp = 4 + P.withPn;
+    const double *zs = z + (size_t)nz*s;
+    double t = scen[(size_t)MSD_SC_COUNT*s + MSD_SC_T0], b = scen[(size_t)MSD_SC_COUNT*s + MSD_SC_V0SQ];
+    double tr = 0, rg = 0, pb = 0, ls = 0;
+    bool stall = false;
+    int done = 0;
+    for (int i = 0; i < n; i++) {
+        const double fel = zs[stp*i], fpb = P.withPn ? zs[stp*i + 1] : 0.0;
+        const double F = fel*M, ds = P.ds[i];
+        double E = 0;
+        if (plant || kind == 2) {
+            const double w = (fel + fpb)*scale, G = msd::track_resistance(Pp, P.grad[i], P.curv[i]);
+            const double b0 = plant ? b : zs[stp*i + stp - 1];
+            if (kind == 2) { const msd::DynLoss D(P.loss, P.lossCoef, M); E = loss_integral(Pp, D, b0, w, fel, G, ds); }
+            if (plant) {
+                double tau, bp;
+                msd::interval_map<double>(Pp, b, w, G, ds, tau, bp);
+                if (!(bp >= P.vminSq) || !isfinite(tau)) { stall = true; break; }      /* (mpc_plant's rule) */
+                t += tau; b = bp;
+            }
+        }
+        if (kind == 1) E = ds*(ct*fmax(F, 0.0) + cr*fmax(-F, 0.0));
+        tr += ds*fmax(F, 0.0); rg += ds*fmin(F, 0.0); pb += ds*(fpb*M); ls += E;
+        done++;
+    }
+    if (!plant) { const int node = stp*n + (n < P.N ? stp - 2 : 0); t = zs[node]; b = zs[node + 1]; }
+    const double v = sqrt(b), kwh = 1e-6/3.6;
+    e[MSD_MPC_EN_TRACTION] = tr*kwh; e[MSD_MPC_EN_REGENERATED] = rg*kwh; e[MSD_MPC_EN_PNBRAKE] = pb*kwh; e[MSD_MPC_EN_LOSSES] = ls*kwh;
+    e[MSD_MPC_EN_T] = t; e[MSD_MPC_EN_V] = v; e[MSD_MPC_EN_INTERVALS] = (double)done;
+    if (!advance) return;
+    rec[MSD_MPC_PS_T] = t; rec[MSD_MPC_PS_V] = v; rec[MSD_MPC_PS_STALLED] = stall ? 1.0 : 0.0;
+    if (stall) { stalled[s] = 1; return; }
+    tnow[s] = fmax(__dmul_rn(t, __dadd_rn(1.0, __dmul_rn(noise, n1[s]))), 0.0);      /* (mpc_advance's arithmetic) */
+    vnow[s] = __dmul_rn(v, __dadd_rn(1.0, __dmul_rn(noise, n2[s])));
+}
+
 }  // namespace
 
 struct msd_mpc {
@@ -279,6 +376,14 @@ struct msd_mpc {
     int ro_nscen = 0, plant_steps = 0;
     bool ro_model = false, ro_plant = false;
     int ps_nscen = 0;                     /* scenarios of the plant states the last run left (0: none) */
+    /* energy account (msd_mpc_energy), one buffer: ct, cr of the plants' own efficiencies [nscen][2] | records [K][nscen][MSD_MPC_EN_COUNT]; en_nscen scenarios are
+     * accounted for (0: no account) and only a run of exactly that many is accepted */
+    double *d_en = nullptr, *d_en_rec = nullptr;
+    int cap_en = 0;                       /* scenarios of d_en */
+    int en_nscen = 0, en_steps = 0;
+    bool en_eta = false;
+    double en_mass = 0;
+    int en_run = 0;                       /* scenarios of the records the last run left (0: none) */
 };
 
 /* the rows and caps of re-solve k under the loop's records, on `st` */
@@ -299,7 +404,7 @@ int msd_mpc_destroy(msd_mpc_handle m)
     if (m->h) { hipSetDevice(m->h->device); hipStreamSynchronize(m->h->stream); m->h->attached_loops--; }
     if (m->twin) m->twin->attached_loops--;
     hipFree(m->d_prof); hipFree(m->d_work); hipFree(m->d_tables); hipFree(m->d_ints); hipFree(m->d_buf); hipFree(m->d_zlog);
-    hipFree(m->d_rs); hipFree(m->d_rows); hipFree(m->d_ro);
+    hipFree(m->d_rs); hipFree(m->d_rows); hipFree(m->d_ro); hipFree(m->d_en);
     if (m->e0) hipEventDestroy(m->e0);
     if (m->e1) hipEventDestroy(m->e1);
     delete m;
@@ -444,6 +549,12 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
                                    + " (msd_mpc_rolling_stock with nscen = 0 clears it)");
     const double *ovr = (ro && m->ro_model) ? m->d_ovr : nullptr;      /* (every launch: the lists carry original scenario indices, so row s stays with scenario s) */
     const bool plant = ro && m->ro_plant;
+    const bool account = m->en_nscen != 0;
+    if (account && nscen != m->en_nscen)
+        return fail(MSD_E_INVALID, "the loop keeps the energy account of " + std::to_string(m->en_nscen) + " scenarios, the run has " + std::to_string(nscen)
+                                   + " (msd_mpc_energy with nscen = 0 clears it)");
+    if (account && plant && m->en_steps != m->plant_steps)
+        return fail(MSD_E_INVALID, "the energy account takes " + std::to_string(m->en_steps) + " steps per interval, the plant " + std::to_string(m->plant_steps));
     for (int s = 0; s < nscen; s++) if (!(T[s] > 0)) return fail(MSD_E_INVALID, "Terminal time must be a strictly positive number!");
     msd_problem *h = m->h;
     if (h->begun) return fail(MSD_E_INVALID, "a batch begun with msd_solve_batch_begin has not been waited for (MSD_WAIT_ALL)");
@@ -465,6 +576,10 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
         m->ps_nscen = 0;
         HIP_TRY(hipMemsetAsync(m->d_stalled, 0, sizeof(int)*(size_t)B, st));
         HIP_TRY(hipMemsetAsync(m->d_ps, 0, sizeof(double)*(size_t)MSD_MPC_PS_COUNT*std::max(K - 1, 1)*B, st));      /* (a record no advance writes reads as zeros) */
+    }
+    if (account) {
+        m->en_run = 0;
+        HIP_TRY(hipMemsetAsync(m->d_en_rec, 0, sizeof(double)*(size_t)MSD_MPC_EN_COUNT*K*B, st));      /* (a record no leg writes reads as zeros) */
     }
     const dim3 tb(256), gb((B + 255)/256);
     auto queue = [&]() { int *q = m->d_queue + m->queue_slot; m->queue_slot = (m->queue_slot + 1) % RING; return q; };
@@ -520,10 +635,21 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
             HIP_TRY(hipMemcpyAsync(m->d_zlog + zoff, m->d_z[cur], sizeof(double)*(size_t)pl.nz*B, hipMemcpyDeviceToDevice, st));
             zoff += (size_t)pl.nz*B;
         }
-        if (k + 1 < K && N - m->stride >= 1 && plant)
+        const bool leg = k + 1 < K && N - m->stride >= 1;
+        if (account) {
+            /* the account of the leg behind this re-solve: with a plant the kernel stands where mpc_plant stands and advances the state too; without one it runs
+             * next to mpc_advance; behind the last re-solve the whole plan, and nothing but the account is written */
+            const int adv = (leg && plant) ? 1 : 0;
+            const size_t row = leg ? (size_t)B*k : 0;      /* (the final leg has no noise: the pointers are not read) */
+            hipLaunchKernelGGL(mpc_energy, gb, tb, 0, st, pl.P, B, leg ? m->stride : N, m->en_steps, m->d_z[cur], pl.nz, m->d_st[cur], m->d_scen, ovr,
+                               plant ? (const double *)m->d_plant : nullptr, m->en_eta ? (const double *)m->d_en : nullptr, m->en_mass, adv, m->noise, m->d_n1 + row, m->d_n2 + row,
+                               m->d_tnow, m->d_vnow, plant ? m->d_stalled : nullptr, adv ? m->d_ps + (size_t)MSD_MPC_PS_COUNT*B*k : nullptr,
+                               m->d_en_rec + (size_t)MSD_MPC_EN_COUNT*B*k);
+        }
+        if (leg && plant && !account)
             hipLaunchKernelGGL(mpc_plant, gb, tb, 0, st, pl.P, B, m->stride, m->plant_steps, m->d_z[cur], pl.nz, m->d_st[cur], m->d_scen, m->d_plant, m->noise,
                                m->d_n1 + (size_t)B*k, m->d_n2 + (size_t)B*k, m->d_tnow, m->d_vnow, m->d_stalled, m->d_ps + (size_t)MSD_MPC_PS_COUNT*B*k);
-        else if (k + 1 < K && N - m->stride >= 1)
+        else if (leg && !plant)
             hipLaunchKernelGGL(mpc_advance, gb, tb, 0, st, B, m->d_z[cur], pl.nz, m->d_st[cur], stp*m->stride + 2 + pl.P.withPn, stp*m->stride + 3 + pl.P.withPn, m->noise,
                                m->d_n1 + (size_t)B*k, m->d_n2 + (size_t)B*k, m->d_tnow, m->d_vnow);
         cur = prev;
@@ -535,6 +661,58 @@ int msd_mpc_run(msd_mpc_handle m, int nscen, const double *T, double initial_tim
     HIP_TRY(hipStreamSynchronize(st));
     if (loop_ms) HIP_TRY(hipEventElapsedTime(loop_ms, m->e0, m->e1));
     if (plant) m->ps_nscen = B;
+    if (account) m->en_run = B;
+    return MSD_OK;
+}
+
+int msd_mpc_energy(msd_mpc_handle m, int nscen, double total_mass, const double *eta, int steps)
+{
+    if (!m) return fail(MSD_E_INVALID, "null handle");
+    if (nscen == 0) { m->en_nscen = 0; m->en_run = 0; return MSD_OK; }      /* (the buffer stays; no run is in flight) */
+    if (nscen < 0) return fail(MSD_E_INVALID, "msd_mpc_energy: bad argument");
+    if (m->rs_nscen && nscen != m->rs_nscen)
+        return fail(MSD_E_INVALID, "the loop holds the speed restrictions of " + std::to_string(m->rs_nscen) + " scenarios: an energy account of " + std::to_string(nscen) + " does not compose with them");
+    if (m->ro_nscen && nscen != m->ro_nscen)
+        return fail(MSD_E_INVALID, "the loop holds the rolling stock of " + std::to_string(m->ro_nscen) + " scenarios: an energy account of " + std::to_string(nscen) + " does not compose with it");
+    if (!std::isfinite(total_mass) || !(total_mass > 0)) return fail(MSD_E_INVALID, "msd_mpc_energy: total_mass must be positive");
+    if (m->ro_nscen && m->ro_plant) {
+        if (steps != m->plant_steps) return fail(MSD_E_INVALID, "msd_mpc_energy: steps must be the plant's plant_steps (" + std::to_string(m->plant_steps) + ")");
+    } else if (steps < 1 || steps > 64) return fail(MSD_E_INVALID, "msd_mpc_energy: steps must be 1 ... 64");
+    const size_t b = (size_t)nscen;
+    std::vector<double> coef;
+    if (eta) {
+        coef.resize(2*b);
+        for (size_t s = 0; s < b; s++) {
+            const double et = eta[2*s], er = eta[2*s + 1];
+            if (!(et > 0) || !(et <= 1) || !(er > 0) || !(er <= 1)) return fail(MSD_E_INVALID, "efficiencies of scenario " + std::to_string(s) + " are not in (0, 1]");
+            coef[2*s] = (1 - et)/et; coef[2*s + 1] = 1 - er;      /* train.py:199-212 */
+        }
+    }
+    msd_problem *h = m->h;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    m->en_nscen = 0; m->en_run = 0;      /* (until the upload has ended) */
+    if (nscen > m->cap_en) {
+        hipFree(m->d_en); m->d_en = nullptr; m->cap_en = 0;
+        HIP_TRY(hipMalloc((void **)&m->d_en, sizeof(double)*(2*b + (size_t)MSD_MPC_EN_COUNT*m->K*b)));
+        m->cap_en = nscen;
+    }
+    m->d_en_rec = m->d_en + 2*b;
+    if (eta) HIP_TRY(hipMemcpy(m->d_en, coef.data(), sizeof(double)*2*b, hipMemcpyHostToDevice));
+    m->en_eta = eta != nullptr; m->en_mass = total_mass; m->en_steps = steps;
+    m->en_nscen = nscen;
+    return MSD_OK;
+}
+
+int msd_mpc_energy_records(msd_mpc_handle m, double *records)
+{
+    if (!m || !records) return fail(MSD_E_INVALID, "bad argument");
+    if (!m->en_nscen) return fail(MSD_E_INVALID, "the loop keeps no energy account (msd_mpc_energy)");
+    if (!m->en_run) return fail(MSD_E_INVALID, "msd_mpc_energy_records: the loop has not run under its account yet");
+    msd_problem *h = m->h;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(records, m->d_en_rec, sizeof(double)*(size_t)MSD_MPC_EN_COUNT*m->K*m->en_run, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MSD_OK;
 }
 
@@ -545,6 +723,8 @@ int msd_mpc_rolling_stock(msd_mpc_handle m, int nscen, const double *model, cons
     if (nscen < 0 || (!model && !plant)) return fail(MSD_E_INVALID, "msd_mpc_rolling_stock: bad argument");
     if (m->rs_nscen && nscen != m->rs_nscen)
         return fail(MSD_E_INVALID, "the loop holds the speed restrictions of " + std::to_string(m->rs_nscen) + " scenarios: rolling stock of " + std::to_string(nscen) + " does not compose with them");
+    if (m->en_nscen && nscen != m->en_nscen)
+        return fail(MSD_E_INVALID, "the loop keeps the energy account of " + std::to_string(m->en_nscen) + " scenarios: rolling stock of " + std::to_string(nscen) + " does not compose with it");
     if (model) {
         bool fused = false;      /* (any kernel of the loop that has the row structure compiled in) */
         for (int k = 0; k < m->K; k++) fused = fused || m->pl[k].fused_family || (m->twin && m->tw[k].fused_family);
@@ -602,6 +782,8 @@ int msd_mpc_speed_restrictions(msd_mpc_handle m, const double *origin, int nscen
     if (nscen < 0 || !origin || !count || !records) return fail(MSD_E_INVALID, "msd_mpc_speed_restrictions: bad argument");
     if (m->ro_nscen && nscen != m->ro_nscen)
         return fail(MSD_E_INVALID, "the loop holds the rolling stock of " + std::to_string(m->ro_nscen) + " scenarios: speed restrictions of " + std::to_string(nscen) + " do not compose with it");
+    if (m->en_nscen && nscen != m->en_nscen)
+        return fail(MSD_E_INVALID, "the loop keeps the energy account of " + std::to_string(m->en_nscen) + " scenarios: speed restrictions of " + std::to_string(nscen) + " do not compose with it");
     if (max_per_scenario < 1 || max_per_scenario > MSD_RS_MAX)
         return fail(MSD_E_INVALID, "msd_mpc_speed_restrictions: max_per_scenario must be 1 ... " + std::to_string(MSD_RS_MAX));
     const int K = m->K;

@@ -67,6 +67,7 @@ MPC_RS_COUNT = 4      # MSD_MPC_RS_COUNT: (begin [m], end [m], velocity [m/s], f
 MPC_PL = dict(SR0=0, SR1=1, SR2=2, FORCE_SCALE=3, COUNT=4)      # MSD_MPC_PL_*: the plant of a scenario (msd_mpc_rolling_stock)
 MPC_PS = dict(T=0, V=1, STALLED=2, COUNT=3)                      # MSD_MPC_PS_*: the plant's state behind an advance (msd_mpc_plant_states)
 MPC_PLANT_STEPS_MAX = 64
+MPC_EN = dict(TRACTION=0, REGENERATED=1, PNBRAKE=2, LOSSES=3, T=4, V=5, INTERVALS=6, COUNT=7)      # MSD_MPC_EN_*: the energy account of a leg (msd_mpc_energy)
 
 
 class DeviceError(RuntimeError):
@@ -149,6 +150,8 @@ def lib():
         L.msd_mpc_limit_rows.argtypes = [vp, ctypes.c_int, _dptr]
         L.msd_mpc_rolling_stock.argtypes = [vp, ctypes.c_int, _dptr, _dptr, ctypes.c_int]
         L.msd_mpc_plant_states.argtypes = [vp, _dptr]
+        L.msd_mpc_energy.argtypes = [vp, ctypes.c_int, ctypes.c_double, _dptr, ctypes.c_int]
+        L.msd_mpc_energy_records.argtypes = [vp, _dptr]
 
         _lib = L
 
@@ -818,6 +821,34 @@ class DeviceLoop():
         states = np.zeros((max(self.K - 1, 0), max(B, 1), MPC_PS['COUNT']))
         _check(lib().msd_mpc_plant_states(self._m, _d(states)))
         return states[:, :B]
+
+    def energy(self, B=None, totalMass=0.0, eta=None, steps=8):
+        """
+        The energy account inside the loop (msd_mpc_energy): B scenarios, totalMass = mass rho of the problems' train (a scenario with a model row uses its own),
+        eta (B, 2) efficiencies etaTraction, etaRgBrake of the plants or None (the problems' loss model), steps Runge-Kutta steps per interval (the plant's where the
+        loop holds one).  Every run of exactly B scenarios keeps the account until it is cleared.  B None: clears it.
+        """
+
+        L = lib()
+        if B is None:
+            _check(L.msd_mpc_energy(self._m, 0, 0.0, None, 0))
+            self._en = 0
+            return self
+        if eta is not None:
+            eta = np.ascontiguousarray(eta, dtype=np.float64)
+            if eta.shape != (int(B), 2):
+                raise ValueError("efficiencies must have shape ({}, 2)!".format(int(B)))
+        _check(L.msd_mpc_energy(self._m, int(B), float(totalMass), _d(eta) if eta is not None else None, int(steps)))
+        self._en = int(B)
+        return self
+
+    def energy_records(self):
+        "(K, B, MPC_EN['COUNT']): the account of every leg of the last run; record K - 1 is the final leg (msd_mpc_energy_records)."
+
+        B = getattr(self, '_en', 0)
+        records = np.zeros((self.K, max(B, 1), MPC_EN['COUNT']))
+        _check(lib().msd_mpc_energy_records(self._m, _d(records)))
+        return records[:, :B]
 
     def close(self):
 

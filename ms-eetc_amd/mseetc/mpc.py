@@ -238,6 +238,203 @@ def plantAdvance(solver, z, t0, v0sq, plantRows, plantSteps, stride):
     return _plantAdvance(solver.points, solver.withPnBrake, solver.train.g, solver.train.rho, float(solver.velocityMin)**2, z, t0, v0sq, plantRows, plantSteps, stride)
 
 
+KWH = 1e-6/3.6      # Nm -> kWh (utils.py:243)
+ENERGY_KEYS = ('traction', 'regenerated', 'pnBrake', 'losses')
+
+
+def _plantEnergy(points, withPnBrake, g, rho, vminSq, z, t0, v0sq, plantRows, steps, n, totalMass, modelRows, lossKind, ct, cr, lossFun):
+    """
+    plantEnergy behind the solver: `points` the grid frame, g and rho the train's, vminSq the square of the minimum velocity, modelRows (B, >= 3) the specific
+    Davis coefficients of the scenarios' models, lossKind 0 / 1 / 2 (utils.LOSS_*) with the slopes ct, cr (B,) of kind 1 and the callable L(F [N], v) [W] of kind 2.
+    """
+
+    from ._device import MPC_PL
+    from .utils import LOSS_STATIC, LOSS_DYNAMIC
+
+    z = np.atleast_2d(np.asarray(z, dtype=float))
+    B = z.shape[0]
+    pn = int(bool(withPnBrake))
+    stp = 4 + pn
+    pos = points.index.values.astype(float)
+    ds = np.diff(pos)
+    N = len(ds)
+    n = int(n)
+    if not 0 <= n <= N or z.shape[1] != stp*N + 2:
+        raise ValueError("A leg of {} intervals on a plan of {} ({} variables)!".format(n, N, z.shape[1]))
+    grad = points['Gradient [permil]'].values.astype(float)/1e3
+    curv = np.abs(points['Curvature [1/m]'].values.astype(float))
+    M = np.broadcast_to(np.asarray(totalMass, dtype=float), (B,))
+    withPlant = plantRows is not None
+    rows = np.atleast_2d(np.asarray(plantRows if withPlant else modelRows, dtype=float))
+    sr0, sr1, sr2 = rows[:, MPC_PL['SR0']], rows[:, MPC_PL['SR1']], rows[:, MPC_PL['SR2']]
+    scale = rows[:, MPC_PL['FORCE_SCALE']] if withPlant else 1.0
+    table = lossKind == LOSS_DYNAMIC
+    t = np.broadcast_to(np.asarray(t0, dtype=float), (B,)).copy()
+    b = np.broadcast_to(np.asarray(v0sq, dtype=float), (B,)).copy()
+    stalled = np.zeros(B, dtype=bool)
+    done = np.zeros(B, dtype=int)
+    acc = {key: np.zeros(B) for key in ENERGY_KEYS}      # [Nm]
+    m = int(steps)
+    h = 1.0/m
+
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        for i in range(n):
+            fel = z[:, stp*i]
+            fpb = z[:, stp*i + 1] if pn else np.zeros(B)
+            F, Fpn = fel*M, fpb*M
+            lossE = np.zeros(B)
+            if withPlant or table:
+                c = curv[i]
+                cres = g*0.5*c/(1 - 30*c) if c <= 1.0/300.0 else g*0.65*c/(1 - 55*c)      # train.py:252-253
+                G = g*grad[i]*(1/rho) + cres*(1/rho)
+                w = (fel + fpb)*scale
+                fb = lambda x: ((w - (sr0 + (np.sqrt(x)*sr1 + x*sr2))) - G)*(2*ds[i])      # (_plantAdvance's)
+                ft = lambda x: ds[i]/np.sqrt(x)
+
+                def fe(x):
+                    "d(E)/d(sigma) [Nm] on the unit interval: ds L(F, v)/v"
+                    v = np.sqrt(x)
+                    return np.array([ds[i]*lossFun(F[s], v[s])/v[s] for s in range(B)]) if table else np.zeros(B)
+
+                bi = b.copy() if withPlant else z[:, stp*i + stp - 1].copy()      # (without a plant every interval restarts from the plan's own b_i)
+                tau = np.zeros(B)
+                for _ in range(m):
+                    k1b, k1t, k1e = fb(bi), ft(bi), fe(bi)
+                    b2 = bi + k1b*(0.5*h)
+                    k2b, k2t, k2e = fb(b2), ft(b2), fe(b2)
+                    b3 = bi + k2b*(0.5*h)
+                    k3b, k3t, k3e = fb(b3), ft(b3), fe(b3)
+                    b4 = bi + k3b*h
+                    k4b, k4t, k4e = fb(b4), ft(b4), fe(b4)
+                    bi = bi + ((k1b + k2b*2.0) + (k3b*2.0 + k4b))*(h/6)
+                    tau = tau + ((k1t + k2t*2.0) + (k3t*2.0 + k4t))*(h/6)
+                    lossE = lossE + ((k1e + k2e*2.0) + (k3e*2.0 + k4e))*(h/6)
+                if withPlant:
+                    stalled |= ~stalled & (~(bi >= vminSq) | ~np.isfinite(tau))      # (_plantAdvance's rule)
+                    t = np.where(stalled, t, t + tau)
+                    b = np.where(stalled, b, bi)
+            if lossKind == LOSS_STATIC:
+                lossE = ds[i]*(ct*np.maximum(F, 0.0) + cr*np.maximum(-F, 0.0))      # (the speed cancels: train.py:199-212)
+            go = ~stalled
+            done += go
+            acc['traction'] += np.where(go, ds[i]*np.maximum(F, 0.0), 0.0)
+            acc['regenerated'] += np.where(go, ds[i]*np.minimum(F, 0.0), 0.0)
+            acc['pnBrake'] += np.where(go, ds[i]*Fpn, 0.0)
+            acc['losses'] += np.where(go, lossE, 0.0)
+
+    if not withPlant:      # the plan's node n, read
+        node = stp*n + (stp - 2 if n < N else 0)
+        t, b = z[:, node].copy(), z[:, node + 1].copy()
+    out = {key: a*KWH for key, a in acc.items()}
+    out.update(t=t, v=np.sqrt(b), intervals=done, stalled=stalled)
+
+    return out
+
+
+def _etaSlopes(eta, B):
+    "(ct, cr) (B,) of (B, 2) efficiencies etaTraction, etaRgBrake (train.py:199-212), validated"
+
+    eta = np.asarray(eta, dtype=float)
+    if eta.shape != (B, 2) or not np.all(np.isfinite(eta)) or np.any(eta <= 0) or np.any(eta > 1):
+        raise ValueError("Plant efficiencies are given as ({}, 2) values in (0, 1]!".format(B))
+    return (1 - eta[:, 0])/eta[:, 0], 1 - eta[:, 1]
+
+
+def plantEnergy(solver, z, t0, v0sq, plantRows, steps, n, totalMass, eta=None, modelRows=None):
+    """
+    The energy account of one leg of a loop: the numpy statement of csrc/msd_mpc.hip: mpc_energy, the definition the device is held to (include/mseetc_mpc.h:
+    msd_mpc_energy).  The first `n` intervals of the plans `z` (B, nz) on the solver's grid, per scenario; forces in newtons are the plan's specific forces times
+    `totalMass` (scalar or (B,): mass rho of the scenario's MODEL -- the plant's traction equipment receives the commanded newtons whatever the plant weighs).
+    With `plantRows` (B, MPC_PL['COUNT']) the speed trajectory is plantAdvance's, from (`t0`, `v0sq`) with the same arithmetic, stall rule and bits: a stall ends the
+    leg in front of the interval that stalled it, and what was spent up to there counts.  With plantRows None the plan is the plant: every interval restarts from
+    the plan's own b_i, integrated with the model's specific Davis coefficients (`modelRows` (B, >= 3); None: the solver's train) and force_scale 1 -- what the
+    reference's post-processing does per interval (utils.py:261-289) -- and the state at the end is the plan's node n, read.
+    Per interval, summed over the intervals completed (reference: utils.py:243-257, :291): traction ds max(F_el, 0), regenerated ds min(F_el, 0), pnBrake ds F_pn, and
+    losses: with constant efficiencies (the train's, or `eta` (B, 2): etaTraction, etaRgBrake of the PLANT) ds (ct max(F, 0) + cr max(-F, 0)) with ct = (1 - eta_t)/eta_t,
+    cr = 1 - eta_r, in closed form (the speed cancels); with a loss table (efficiency.DynamicLosses / TabulatedLosses, no eta) the integral of L(F_el, v)/v over the
+    interval as a third component of the same Runge-Kutta steps, k_E(x) = ds L(F, sqrt(x))/sqrt(x) at the four stage values of b, combined like the running time;
+    without a loss model and without eta 0.
+    Returns a dict: traction, regenerated, pnBrake, losses [kWh] (B,), t, v (B,) the state at the end of the leg (before any noise), intervals (B,) completed, stalled (B,).
+    """
+
+    from .utils import classifyLosses, LOSS_STATIC, LOSS_DYNAMIC
+
+    z = np.atleast_2d(np.asarray(z, dtype=float))
+    B = z.shape[0]
+    train = solver.train
+    if int(steps) != steps or not 1 <= int(steps) <= 64:
+        raise ValueError("steps must be 1 ... 64!")
+    if eta is not None:
+        kind, fun = LOSS_STATIC, None
+        ct, cr = _etaSlopes(eta, B)
+    else:
+        fun = train.lossesCallable()
+        kind, ct, cr = classifyLosses(fun)
+    if modelRows is None:
+        Mt = train.mass*train.rho
+        modelRows = np.repeat(np.array([[train.r0/Mt, train.r1/Mt, train.r2/Mt]]), B, axis=0)
+    M = np.broadcast_to(np.asarray(totalMass, dtype=float), (B,))
+    if not np.all(np.isfinite(M)) or np.any(M <= 0):
+        raise ValueError("totalMass must be positive!")
+
+    return _plantEnergy(solver.points, solver.withPnBrake, train.g, train.rho, float(solver.velocityMin)**2, z, t0, v0sq, plantRows, steps, n, M, modelRows,
+                        kind, ct, cr, fun if kind == LOSS_DYNAMIC else None)
+
+
+def _energyAccount(train, B, energyAccount, plantEtaTraction, plantEtaRgBrake):
+    """
+    (account, eta): whether a loop keeps the energy account, and the (B, 2) efficiencies of the plants or None.  `plantEtaTraction`, `plantEtaRgBrake` (scalars or
+    one value per scenario, in (0, 1]) imply the account; one that is not given is the train's.  Validated like plantMass.
+    """
+
+    if plantEtaTraction is None and plantEtaRgBrake is None:
+        return bool(energyAccount), None
+    eta = np.zeros((B, 2))
+    for j, (a, name) in enumerate(((plantEtaTraction, 'etaTraction'), (plantEtaRgBrake, 'etaRgBrake'))):
+        if a is None:
+            if getattr(train, name, None) is None:
+                raise ValueError("The train has no {}: give both efficiencies of the plant!".format(name))
+            a = getattr(train, name)
+        a = np.asarray(a, dtype=float)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
+            raise ValueError("plant {} of {} scenarios for a batch of {}!".format(name, a.shape[0] if a.ndim == 1 else a.shape, B))
+        eta[:, j] = np.broadcast_to(a, (B,))
+    _etaSlopes(eta, B)
+
+    return True, eta
+
+
+def _legRecord(leg, active):
+    "the log's keys of one leg: a scenario that is not advanced (its re-solve failed, or it stalled earlier) has a zero record with 0 intervals"
+
+    out = {'energy' + key[0].upper() + key[1:]: np.where(active, leg[key], 0.0) for key in ENERGY_KEYS}
+    out['legIntervals'] = np.where(active, leg['intervals'], 0)
+    return out
+
+
+def closedLoopEnergy(log):
+    """
+    The energy the closed loop drew, from the log of a loop run with `energyAccount` (shrinkingHorizon, DeviceLoop.run): per scenario `total` (traction +
+    regenerated + losses: what the objective prices) and the four components [kWh], summed over the legs -- `stride` intervals behind every re-solve but the last,
+    the whole plan behind the last --, `arrivalTime` [s] and `arrivalVelocity` [m/s] (the state at the end of the last leg), and `complete`: every leg ran its full
+    interval count (False for a scenario whose re-solve failed or whose plant stalled: its account ends there).
+    Read `complete` with the totals.  With a plant and plans that brake to the minimum velocity at the platform (the default terminal velocity of 1 m/s is the
+    minimum velocity) the plant usually falls below the minimum in the last interval, and the stall rule ends the final leg in front of it: `complete` is False, and
+    `total`, `arrivalTime` and `arrivalVelocity` are those of the state in front of that interval -- one interval short of the platform -- not of the arrival.
+    """
+
+    if not log or 'energyTraction' not in log[0]:
+        raise ValueError("The log holds no energy account (energyAccount=True)!")
+    out = {key: sum(r['energy' + key[0].upper() + key[1:]] for r in log) for key in ENERGY_KEYS}
+    out['total'] = out['traction'] + out['regenerated'] + out['losses']
+    out['arrivalTime'], out['arrivalVelocity'] = log[-1]['tArrival'].copy(), log[-1]['vArrival'].copy()
+    K = len(log)
+    full = [r['numIntervals'] - log[k + 1]['numIntervals'] if k < K - 1 else r['numIntervals'] for k, r in enumerate(log)]      # (stride; the whole last plan)
+    out['complete'] = np.all([r['legIntervals'] == full[k] for k, r in enumerate(log)], axis=0)
+
+    return out
+
+
 class DeviceLoop():
     """
     The shrinking-horizon loop with its bookkeeping on the device (csrc/msd_mpc.hip, include/mseetc_mpc.h): the grid sequence does not depend
@@ -351,9 +548,14 @@ class DeviceLoop():
         return np.broadcast_to(scen, (int(B), scen.shape[1])).copy()
 
     def run(self, terminalTime, seed=0, initialTime=0.0, initialVelocity=1.0, keepZ=True, speedRestrictions=None, mass=None, r0=None, r1=None, r2=None,
-            plantMass=None, plantR0=None, plantR1=None, plantR2=None, plantSteps=8):
+            plantMass=None, plantR0=None, plantR1=None, plantR2=None, plantSteps=8, energyAccount=False, plantEtaTraction=None, plantEtaRgBrake=None):
         """
         One loop; returns the log of shrinkingHorizon() (list of dicts per re-solve; 'z' None without keepZ) -- `loop_ms` in every entry is the device time of the whole loop.
+        `energyAccount`: the energy the closed loop really spends, kept on the device (msd_mpc_energy; plantEnergy is its statement): every log entry gains
+        'energyTraction', 'energyRegenerated', 'energyPnBrake', 'energyLosses' [kWh] and 'legIntervals' of the leg driven behind its re-solve (`stride` intervals;
+        behind the last re-solve the whole remaining plan), the last entry also 'tArrival', 'vArrival': with a plant the plant's arrival, without one the plan's.
+        closedLoopEnergy(log) sums them.  `plantEtaTraction`, `plantEtaRgBrake` (in (0, 1], scalars or one value per scenario): a plant whose efficiencies are not
+        the model's; they imply the account and change no plan.  Without a plant the loss integral of a loss table takes `plantSteps` Runge-Kutta steps per interval.
         `speedRestrictions`: a sequence of B sequences of (begin [m], end [m], velocity [m/s][, firstResolve]), or one such sequence for every scenario --
         restrictions in route coordinates (0: the first node of the first grid) that are known from re-solve `firstResolve` on (default 0): from then on the
         scenario's re-solves run under restrictedLimits(k, ...), their end speeds clipped to the restricted limits; a restriction the train has passed is
@@ -367,10 +569,13 @@ class DeviceLoop():
         advance: the scenario keeps its last measurement).  ValueError: values the library refuses, plantSteps outside 1 ... 64, a wrong batch length.
         """
 
-        from ._device import MPC, MPC_PS
+        from ._device import MPC, MPC_PS, MPC_EN, MPC_PLANT_STEPS_MAX
 
         T = np.array(np.atleast_1d(np.asarray(terminalTime, dtype=float)), copy=True)
         B = T.shape[0]
+        account, eta = _energyAccount(self.solvers[0].train, B, energyAccount, plantEtaTraction, plantEtaRgBrake)
+        if account and (int(plantSteps) != plantSteps or not 1 <= int(plantSteps) <= MPC_PLANT_STEPS_MAX):
+            raise ValueError("plantSteps must be 1 ... {}!".format(MPC_PLANT_STEPS_MAX))
         sets = self._restrictionSets(speedRestrictions, B) if speedRestrictions is not None else None
         rng = np.random.default_rng(seed)
         n1, n2 = np.zeros((max(self.K - 1, 0), B)), np.zeros((max(self.K - 1, 0), B))
@@ -379,17 +584,23 @@ class DeviceLoop():
         model, plant = _rollingStock(self.solvers[0].train, B, mass, r0, r1, r2, plantMass, plantR0, plantR1, plantR2, plantSteps)
         rows = self.solvers[0]._overrides(B, model['mass'], model['r0'], model['r1'], model['r2']) if model is not None else None      # (the rule of solveBatch)
         restricted = sets is not None and any(sets)
-        states = None
-        if restricted or rows is not None or plant is not None:
+        states, legs = None, None
+        if restricted or rows is not None or plant is not None or account:
             try:
                 if restricted:
                     self.device.speed_restrictions(*self.restrictionRecords(sets, B))
                 if rows is not None or plant is not None:
                     self.device.rolling_stock(rows, plant, plantSteps)
+                if account:
+                    train = self.solvers[0].train
+                    self.device.energy(B, train.mass*train.rho, eta, plantSteps)
                 log, zs, ms = self.device.run(T, initialTime, initialVelocity, n1, n2, keepZ=keepZ)
                 if plant is not None and self.K > 1:
                     states = self.device.plant_states()
+                if account:
+                    legs = self.device.energy_records()
             finally:
+                self.device.energy(None)
                 self.device.rolling_stock(None)
                 self.device.speed_restrictions(None)
         else:      # (no scenario is restricted or has a train of its own: the plain loop)
@@ -403,6 +614,12 @@ class DeviceLoop():
                             kernel_ms=ms/self.K, loop_ms=ms))
             if states is not None and k < self.K - 1:
                 out[-1].update(tPlant=states[k, :, MPC_PS['T']].copy(), vPlant=states[k, :, MPC_PS['V']].copy(), stalled=states[k, :, MPC_PS['STALLED']] > 0)
+            if legs is not None:
+                e = legs[k]
+                out[-1].update(energyTraction=e[:, MPC_EN['TRACTION']].copy(), energyRegenerated=e[:, MPC_EN['REGENERATED']].copy(),
+                               energyPnBrake=e[:, MPC_EN['PNBRAKE']].copy(), energyLosses=e[:, MPC_EN['LOSSES']].copy(), legIntervals=e[:, MPC_EN['INTERVALS']].astype(int))
+                if k == self.K - 1:
+                    out[-1].update(tArrival=e[:, MPC_EN['T']].copy(), vArrival=e[:, MPC_EN['V']].copy())
         return out
 
     def close(self):
@@ -418,7 +635,8 @@ class DeviceLoop():
 def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2, noise=0.0, seed=0,
                      initialTime=0.0, initialVelocity=1.0, terminalVelocity=1.0, device=0, solverFactory=None,
                      warmStart=False, warmMu=1e-2, warmPush=1e-3, dualMu=1e-4, relaxInfeasible=True, lateMargin=5e-3, onDevice=False,
-                     speedRestrictions=None, mass=None, r0=None, r1=None, r2=None, plantMass=None, plantR0=None, plantR1=None, plantR2=None, plantSteps=8):
+                     speedRestrictions=None, mass=None, r0=None, r1=None, r2=None, plantMass=None, plantR0=None, plantR1=None, plantR2=None, plantSteps=8,
+                     energyAccount=False, plantEtaTraction=None, plantEtaRgBrake=None):
     """
     Re-solve `numResolves` times; after each solve the train advances `stride` intervals of the current grid, the
     measured time and speed at that node are perturbed by `noise` (relative, standard normal) and the remaining
@@ -447,6 +665,10 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
     `plantR0`, `plantR1`, `plantR2`, `plantSteps`: the train that actually runs, as in DeviceLoop.run -- with any of them the measured state comes from plantAdvance
     under the planned forces instead of the plan, and the log entries in front of the last one gain 'tPlant', 'vPlant' and 'stalled'.  A substituted solver must
     accept the keywords `mass`, `r0`, `r1`, `r2` in solveBatch when any of them is given, and with a plant return its (B, 4) scenario records as 'scenarios'.
+
+    `energyAccount`, `plantEtaTraction`, `plantEtaRgBrake`: the energy the closed loop really spends, as in DeviceLoop.run -- computed here with plantEnergy on the
+    solutions of every re-solve, so that the two loops stay comparable: the log entries gain 'energyTraction', 'energyRegenerated', 'energyPnBrake', 'energyLosses',
+    'legIntervals', the last one 'tArrival', 'vArrival' (closedLoopEnergy sums them).
     """
 
     if onDevice:
@@ -457,7 +679,8 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
                           warmPush=warmPush, dualMu=dualMu, relaxInfeasible=relaxInfeasible, lateMargin=lateMargin)
         try:
             return loop.run(terminalTime, seed=seed, initialTime=initialTime, initialVelocity=initialVelocity, speedRestrictions=speedRestrictions,
-                            mass=mass, r0=r0, r1=r1, r2=r2, plantMass=plantMass, plantR0=plantR0, plantR1=plantR1, plantR2=plantR2, plantSteps=plantSteps)
+                            mass=mass, r0=r0, r1=r1, r2=r2, plantMass=plantMass, plantR0=plantR0, plantR1=plantR1, plantR2=plantR2, plantSteps=plantSteps,
+                            energyAccount=energyAccount, plantEtaTraction=plantEtaTraction, plantEtaRgBrake=plantEtaRgBrake)
         finally:
             loop.close()
 
@@ -470,9 +693,24 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
     model, plant = _rollingStock(train, B, mass, r0, r1, r2, plantMass, plantR0, plantR1, plantR2, plantSteps)
     own = (lambda idx=slice(None): {key: a[idx] for key, a in model.items()}) if model is not None else (lambda idx=None: {})
     stalled = np.zeros(B, dtype=bool)
-    if plant is not None:
+    account, eta = _energyAccount(train, B, energyAccount, plantEtaTraction, plantEtaRgBrake)
+    if plant is not None or account:
         from .ocp import OptionsCasadiSolver
         vminPlant = float(OptionsCasadiSolver(optsDict).minimumVelocity)
+    if account:
+        # the account of every leg: plantEnergy on the re-solve's solutions (include/mseetc_mpc.h: msd_mpc_energy)
+        from ._device import MPC_PLANT_STEPS_MAX
+        from .utils import classifyLosses, LOSS_STATIC, LOSS_DYNAMIC
+        if int(plantSteps) != plantSteps or not 1 <= int(plantSteps) <= MPC_PLANT_STEPS_MAX:      # (without a plant: the steps of the table's loss integral)
+            raise ValueError("plantSteps must be 1 ... {}!".format(MPC_PLANT_STEPS_MAX))
+        if eta is not None:
+            lossModel = (LOSS_STATIC,) + _etaSlopes(eta, B) + (None,)
+        else:
+            lossModel = classifyLosses(train.lossesCallable())
+            lossModel = lossModel + (train.lossesCallable() if lossModel[0] == LOSS_DYNAMIC else None,)
+        own0 = model if model is not None else dict(mass=np.full(B, float(train.mass)), r0=np.full(B, float(train.r0)), r1=np.full(B, float(train.r1)), r2=np.full(B, float(train.r2)))
+        massModel = own0['mass']*train.rho
+        rowsModel = np.stack([own0['r0']/massModel, own0['r1']/massModel, own0['r2']/massModel], axis=1)
 
     N = int(optsDict.get('numIntervals', 100))
     t_now = np.full(B, float(initialTime))
@@ -610,6 +848,28 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
 
             last = solver
 
+            def scenariosNow():
+                "the scenario records of this re-solve (its clipped v0^2, under the restrictions of this re-solve): what a plant starts from"
+                if 'scenarios' in res:
+                    return np.asarray(res['scenarios'])
+                if hasattr(solver, '_scenarios'):
+                    return solver._scenarios(T, t_now, terminalVelocity, v_now, solver._restrictions(setsNow) if setsNow is not None else None)
+                raise ValueError("With a plant a substituted solver returns its scenario records as 'scenarios' from solveBatch!")
+
+            if account:
+                # the leg driven behind this re-solve: `stride` intervals, behind the last re-solve the whole plan (no noise, nothing measured any more)
+                final = k + 1 >= numResolves or Nk - stride < 1
+                active = (res['status'] >= 0) & ~stalled      # (a scenario whose re-solve failed or that stalled earlier is not advanced: a zero record)
+                if active.any():
+                    zLeg = np.where(active[:, None], res['z'], res['z'][np.flatnonzero(active)[0]])      # (the rows that are not advanced are not read)
+                    leg = _plantEnergy(solver.points, solver.withPnBrake, train.g, train.rho, vminPlant**2, zLeg, t_now, scenariosNow()[:, 2] if plant is not None else v_now*v_now,
+                                       plant, plantSteps, Nk if final else stride, massModel, rowsModel, *lossModel)
+                else:
+                    leg = dict({key: np.zeros(B) for key in ENERGY_KEYS}, t=np.zeros(B), v=np.zeros(B), intervals=np.zeros(B, dtype=int))
+                log[-1].update(_legRecord(leg, active))
+                if final:
+                    log[-1].update(tArrival=np.where(active, leg['t'], 0.0), vArrival=np.where(active, leg['v'], 0.0))
+
             if Nk - stride < 1:
                 break
 
@@ -624,12 +884,7 @@ def shrinkingHorizon(train, track, optsDict, terminalTime, numResolves, stride=2
             if plant is not None and k + 1 < numResolves:      # (behind the last re-solve nothing is measured any more)
                 # the train that runs is the plant, not the plan: from the re-solve's own initial state under the planned forces (include/mseetc_mpc.h: msd_mpc_rolling_stock)
                 # (its clipped v0^2: the scenario records of the solve, under the restrictions of this re-solve)
-                if 'scenarios' in res:
-                    scenNow = np.asarray(res['scenarios'])
-                elif hasattr(solver, '_scenarios'):
-                    scenNow = solver._scenarios(T, t_now, terminalVelocity, v_now, solver._restrictions(setsNow) if setsNow is not None else None)
-                else:
-                    raise ValueError("With a plant a substituted solver returns its scenario records as 'scenarios' from solveBatch!")
+                scenNow = scenariosNow()
                 tP, vP, now = _plantAdvance(solver.points, solver.withPnBrake, train.g, train.rho, vminPlant**2, res['z'], t_now, scenNow[:, 2], plant, plantSteps, stride)
                 moved = ok & ~stalled      # (a scenario whose re-solve failed or that has stalled keeps its last measurement: its record holds that)
                 stalled = stalled | (moved & now)
